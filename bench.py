@@ -547,6 +547,36 @@ def cpu_baseline(level: int, rand_channels: int, batch: int, iters: int):
                       f"(forward/backward only, reference-as-executed work incl. its non-detached D step)"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, last, gen, disc, optim_gen, optim_disc) -> None:
+    """`--dump-outputs DIR`: what the last timed step handed its caller -- the loss dicts of its critic and generator updates --
+    and the state it left behind: every weight of both nets and their Adam moments (with beta1 = 0, `exp_avg` is the last
+    update's gradient itself), as float32 DIR/<name>.npy.  About 30 MB at any level; should a wide --rand-channels take the total
+    over 64 MB, every array is cut to the same fraction by a fixed index sample seeded from its name."""
+    import zlib
+    import numpy as np
+    arrays = {}
+    for kind, out in zip(("d_step", "g_step"), last):
+        for k, v in out.items():
+            arrays[f"{kind}.{k}"] = v
+    for tag, net, opt in (("gen", gen, optim_gen), ("disc", disc, optim_disc)):
+        for name, p in net.named_parameters():
+            arrays[f"{tag}.{name}"] = p
+            for k in ("exp_avg", "exp_avg_sq"):
+                if k in opt.state.get(p, {}):
+                    arrays[f"{tag}.{name}.{k}"] = opt.state[p][k]
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    frac = min(1.0, (DUMP_LIMIT_BYTES - (1 << 20)) / sum(a.nbytes for a in arrays.values()))  # (1 MiB for the .npy headers)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if frac < 1.0:
+            idx = np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, max(1, int(a.size * frac)), replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def launch_ranks(n: int, argv) -> int:
     """`python -m torch.distributed.run --standalone --local-addr 127.0.0.1 --nnodes=1 --nproc-per-node n bench.py argv` as
     a child process with inherited stdout / stderr; returns its exit code.  MG_BENCH_LAUNCHER (a command line) replaces
@@ -579,7 +609,11 @@ def main():
     ap.add_argument("--cpu-batch", type=int, default=64)
     ap.add_argument("--no-cadence", action="store_true",
                     help="skip the 5 critic : 1 generator `secondary` record (profiling runs: the trace then holds D+G steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (losses, weights, Adam moments) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
         # dmabuf IPC (RCCL between processes needs it on this image): in THIS process, before the first HIP call -- a launcher that
@@ -628,8 +662,7 @@ def main():
     x_real = torch.rand(args.batch, 2, side, side, device=device, generator=data_rng) * 2 - 1
 
     def one_step():
-        stepper.d_step(x_real, alpha)
-        stepper.g_step(args.batch, alpha, device)
+        return stepper.d_step(x_real, alpha), stepper.g_step(args.batch, alpha, device)
 
     def barrier():
         if world > 1:
@@ -644,7 +677,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        one_step()
+        last = one_step()
     stepper.finish()
     torch.cuda.synchronize()
     barrier()
@@ -662,6 +695,8 @@ def main():
         ranks_seen, rank_ms = int(round(float(ones.item()))), [1e3 * float(tmin.item()) / args.steps, 1e3 * elapsed / args.steps]
     ms_per_step = 1e3 * elapsed / args.steps
     images_per_s = world * args.batch * args.steps / elapsed
+    if args.dump_outputs and rank == 0:  # (before the cadence record below updates the nets further)
+        dump_outputs(args.dump_outputs, last, gen, disc, optim_gen, optim_disc)
 
     # secondary figure: the reference's own cadence, five critic updates per generator update (train.py:189);
     # images/s counts the real images consumed (one batch per critic update).  Single GPU only.

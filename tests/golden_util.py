@@ -30,9 +30,10 @@ def sample_idx(numel: int) -> np.ndarray:
 
 
 def check_tensor(g, name, t, rtol_max, what=""):
-    """Compare tensor t with the golden record `name` (subsample + sum + l2); tolerance is max-norm relative."""
-    t = t.detach().cpu().to(torch.float32).contiguous().reshape(-1)
+    """Compare tensor t with the golden record `name` (subsample + sum + l2), in the record's precision (float32, or float64 for
+    the *_f64.npz fixtures); tolerance is max-norm relative."""
     samp = g[name + "|samp"]
+    t = t.detach().cpu().to(torch.float64 if samp.dtype == np.float64 else torch.float32).contiguous().reshape(-1)
     maxabs = float(g[name + "|maxabs"])
     idx = sample_idx(t.numel())
     got = t.numpy()[idx]

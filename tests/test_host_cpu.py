@@ -381,3 +381,45 @@ def test_native_sample_writer_writes_what_torch_save_writes(tmp_path):
     rc = _lib.load().mg_pt_write_samples(ctypes.c_void_p(rows.data_ptr()), 1, rows[0].numel(), os.fsencode(str(tmp_path / "no" / "x.pt")) + b"\0",
                                          tp.prefix, len(tp.prefix), suffixes, len(suffixes) // 5, -1, 0)
     assert rc != 0 and b"cannot open" in _lib.load().mg_last_error()
+
+
+def test_bench_dump_outputs_names_dtype_cap_and_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one float32 .npy per loss of the last step, per weight of both nets and per Adam moment; the weights
+    as they are; over the size cap every array is cut to one fixed sample of its own values, the same from call to call."""
+    import os
+    import types
+    import bench
+    from musicgan_amd.networks import Discriminator, Generator
+    torch.manual_seed(0)
+    gen, disc = Generator(8), Discriminator(7)
+    gen.next_layer()
+    disc.next_layer()
+
+    def opt(net):  # Adam state on every other tensor (tensors without a gradient have none)
+        return types.SimpleNamespace(state={p: {"step": torch.tensor(3.0), "exp_avg": torch.randn_like(p),
+                                                "exp_avg_sq": torch.rand_like(p)} for p in list(net.parameters())[::2]})
+    og, od = opt(gen), opt(disc)
+    last = ({"disc_loss": torch.tensor(-0.5), "grad_pen": torch.tensor(9.5)}, {"gen_loss": torch.tensor(0.25)})
+    want = {"d_step.disc_loss", "d_step.grad_pen", "g_step.gen_loss"}
+    for tag, net, o in (("gen", gen, og), ("disc", disc, od)):
+        for k, p in net.named_parameters():
+            want.add(f"{tag}.{k}")
+            if p in o.state:
+                want.update({f"{tag}.{k}.exp_avg", f"{tag}.{k}.exp_avg_sq"})
+
+    def dump(d):
+        bench.dump_outputs(str(d), last, gen, disc, og, od)
+        return {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+    full = dump(tmp_path / "full")
+    assert set(full) == want and all(a.dtype == np.float32 for a in full.values())
+    assert float(full["g_step.gen_loss"]) == 0.25
+    for k, p in gen.named_parameters():
+        assert np.array_equal(full[f"gen.{k}"], p.detach().numpy())
+    total = sum(a.nbytes for a in full.values())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", (1 << 20) + total // 4)  # (1 MiB is set aside for the .npy headers)
+    cut, cut2 = dump(tmp_path / "cut"), dump(tmp_path / "cut2")
+    assert set(cut) == want and sum(a.nbytes for a in cut.values()) <= total // 4 + 4 * len(cut)  # (>= 1 value per array)
+    assert sum(os.path.getsize(tmp_path / "cut" / f) for f in os.listdir(tmp_path / "cut")) <= bench.DUMP_LIMIT_BYTES
+    for k, a in cut.items():
+        assert a.dtype == np.float32 and np.array_equal(a, cut2[k])
+        assert np.isin(a, full[k]).all()

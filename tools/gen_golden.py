@@ -489,6 +489,70 @@ def audio_config5_case():
     print("wrote", path, f"({os.path.getsize(path) / 1024:.0f} KiB)")
 
 
+def progan_case_f64(tag):
+    """The step of tests/golden/progan_<tag>.npz run by the REFERENCE in float64 -> progan_<tag>_f64.npz (float64 records, same
+    names).  The fp32 records are each capture host's own rounding: the float64 ones pin the oracle's restatement to the
+    reference independently of the CPU that runs the test.  Same seed, same fp32 init and inputs, nets and inputs widened to
+    float64 (the penalty's eps is drawn in fp32 from the same seed, as the fp32 case draws it)."""
+    g = np.load(os.path.join(OUT, f"progan_{tag}.npz"), allow_pickle=False)
+    nets = load_networks()
+    seed, alpha, batch = int(g["seed"]), float(g["alpha"]), int(g["batch"])
+    torch.manual_seed(seed)
+    gen = nets.Generator(int(g["rand_channels"]), end_layer=int(g["g_end_layer"]))
+    disc = nets.Discriminator(start_layer=int(g["d_start_layer"]))
+    for _ in range(int(g["n_grow"])):
+        gen.next_layer()
+        disc.next_layer()
+    if float(g["wscale"]) != 1.0:
+        _scale_weights((gen, disc), float(g["wscale"]))
+    gen, disc = gen.double(), disc.double()
+    z, z2, x_real = (torch.from_numpy(g[k]).double() for k in ("z", "z2", "x_real"))
+    store = {}
+
+    def put(name, t):
+        t = t.detach().double().contiguous().reshape(-1)
+        store[name + "|samp"] = t.numpy()[sample_idx(t.numel())]
+        store[name + "|l2"] = np.float64(t.norm().item())
+        store[name + "|maxabs"] = np.float64(t.abs().max().item())
+
+    optim_gen = torch.optim.Adam(gen.parameters(), lr=1e-3, betas=(0.0, 0.9))
+    optim_disc = torch.optim.Adam(disc.parameters(), lr=1e-3, betas=(0.0, 0.9))
+    x_fake = gen(z, alpha)
+    out_real, out_fake = disc(x_real, alpha), disc(x_fake, alpha)
+    d_loss = nets.wasserstein_discriminator_loss(out_real, out_fake)
+    torch.manual_seed(seed + 2000)
+    gp = disc.gradient_penalty(x_real, x_fake, alpha)
+    gen.zero_grad()
+    disc.zero_grad()
+    (d_loss + gp).backward()
+    store.update(x_fake=x_fake.detach().numpy(), out_real=out_real.detach().numpy(), out_fake=out_fake.detach().numpy(),
+                 disc_loss=np.float64(d_loss.item()), grad_pen=np.float64(gp.item()))
+    for k, p in disc.named_parameters():
+        if p.grad is not None:
+            put(f"dstep_dgrad|{k}", p.grad)
+    for k, p in gen.named_parameters():
+        if p.grad is not None:
+            put(f"dstep_ggrad|{k}", p.grad)
+    optim_disc.step()
+    for k, p in disc.named_parameters():
+        put(f"dstep_dparam|{k}", p)
+    x_fake2 = gen(z2, alpha)
+    g_loss = nets.wasserstein_generator_loss(disc(x_fake2, alpha))
+    gen.zero_grad()
+    disc.zero_grad()
+    g_loss.backward()
+    store.update(x_fake2=x_fake2.detach().numpy(), gen_loss=np.float64(g_loss.item()))
+    for k, p in gen.named_parameters():
+        if p.grad is not None:
+            put(f"gstep_ggrad|{k}", p.grad)
+    optim_gen.step()
+    for k, p in gen.named_parameters():
+        put(f"gstep_gparam|{k}", p)
+    path = os.path.join(OUT, f"progan_{tag}_f64.npz")
+    np.savez_compressed(path, **store)
+    print(f"wrote {path} ({os.path.getsize(path) / 1024:.0f} KiB)")
+
+
 KINK_MARGIN = 3e-6
 
 
@@ -514,6 +578,11 @@ if __name__ == "__main__":
     if "--config5-only" in sys.argv:
         audio_config5_case()
         sys.exit(0)
+    if "--f64-only" in sys.argv:  # float64 companions of the progan fixtures already written
+        for tag in ("l0_rc8", "l1_rc8_fade", "l3_rc32_fade", "l2_direct", "l2_rc16_fade_scaled", "l2_rc16_gpnorm1",
+                    "l2_rc16_gpnorm3"):
+            progan_case_f64(tag)
+        sys.exit(0)
     scan_seed("l0_rc8", 11, rand_channels=8, n_grow=0, alpha=1.0, batch=3)
     scan_seed("l1_rc8_fade", 12, rand_channels=8, n_grow=1, alpha=0.37, batch=3)
     scan_seed("l3_rc32_fade", 13, rand_channels=32, n_grow=3, alpha=0.37, batch=2)
@@ -523,6 +592,8 @@ if __name__ == "__main__":
     # so (||g|| - 1) takes both signs) and ~3 (all positive)
     scan_seed("l2_rc16_gpnorm1", 16, target_norm=1.0, rand_channels=16, n_grow=2, alpha=0.5, batch=4)
     scan_seed("l2_rc16_gpnorm3", 16, target_norm=3.0, rand_channels=16, n_grow=2, alpha=0.5, batch=4)
+    for tag in ("l0_rc8", "l1_rc8_fade", "l3_rc32_fade", "l2_direct", "l2_rc16_fade_scaled", "l2_rc16_gpnorm1", "l2_rc16_gpnorm3"):
+        progan_case_f64(tag)
     trajectory_case("trajectory", seed=21, rand_channels=8, batch=3, iters=16, fadein=[1, 12, 12, 12, 12, 12, 12, 12],
                     train_lengths=[15, 15, 15, 15, 15, 15, 15])
     transforms_case()
