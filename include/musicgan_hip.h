@@ -363,6 +363,26 @@ size_t mg_stft_1024_pcm_ws_bytes(int64_t L, int channels, int kind);
 int mg_stft_1024_pcm(const void* pcm, int kind, int channels, float* out_re, float* out_im, void* ws, size_t ws_bytes, int64_t L,
                      mg_stream_t stream);
 
+/* ------------------------------------------------------------------ resampling [torchaudio.functional.resample with its defaults]
+ * What a user of the reference calls in front of wav_to_stft for a file that is not at 44.1 kHz (functions.py:45 accepts no other
+ * rate): sinc_interp_hann, lowpass_filter_width = lpw, rolloff.  With o / n = orig_freq / new_freq reduced by their gcd,
+ * base = min(o, n) * rolloff, w = ceil(lpw * o / base), output m = T n + p is sum_k xpad[T o + k] h_p[k] over the 2w + o taps of
+ * torchaudio's row p (xpad = x zero-padded by (w, w + o)), truncated to ceil(n L / o) outputs; orig_freq == new_freq is the identity.
+ * Only 2w + 1 consecutive taps per row differ from a rounding of zero (<= 1.3e-49 at the defaults): the bank keeps those.
+ * mg_resample_len: ceil(n L / o) (L when the rates are equal); -1 for bad arguments.  Host only. */
+int64_t mg_resample_len(int64_t L, int orig_freq, int new_freq);
+/* bytes of the compact bank: float32 taps [phases = n][taps = 2w + 1], then int32 start[n] = floor(o p / n), the index in
+ * torchaudio's row p of compact tap 0 (equal rates: one phase, one unit tap).  0 for bad arguments.  Host only. */
+size_t mg_resample_bank_size(int orig_freq, int new_freq, int lowpass_filter_width, double rolloff, int* phases, int* taps);
+/* fills the bank in HOST memory: computed in float64 with torchaudio's order of operations, rounded once to float32. */
+int mg_resample_bank(int orig_freq, int new_freq, int lowpass_filter_width, double rolloff, void* bank, size_t bank_bytes);
+/* out[r][m], m < mg_resample_len(L, ..): the resampled mono signal of `rows` rows of L PCM frames each (row r starts at frame
+ * r * row_stride; frames of `channels` interleaved samples of kind MG_PCM_*), normalised and averaged over channels on load
+ * exactly as mg_pcm_to_mono does; bank: the device copy of mg_resample_bank's output for the same arguments.  One launch.
+ * Taps per output are accumulated in a fixed order (x_0 h_0, then FMAs j = 1 .. 2w), so equal inputs give equal bits. */
+int mg_resample_pcm(const void* pcm, int kind, int channels, int rows, int64_t row_stride, int64_t L, int orig_freq, int new_freq,
+                    int lowpass_filter_width, double rolloff, const void* bank, size_t bank_bytes, float* out, mg_stream_t stream);
+
 /* ------------------------------------------------------------------ multi-layer chains on small maps
  * The <= 4x4 ends of both networks -- the generator's first blocks [generator.py:15-40,67-76: conv3x3 -> LeakyReLU -> PixelNorm
  * -> Upsample -> conv3x3 -> LeakyReLU -> PixelNorm] and the critic's last blocks + classifier [discriminator.py:14-34,60-70,

@@ -4,12 +4,13 @@ library, `view_audio` pulls in matplotlib)."""
 import argparse
 import importlib
 
-# mode -> (module, function, [(flags, kwargs)], lambda args: call arguments)
+# mode -> (module, function, [(flags, kwargs)], lambda args: positional call arguments[, lambda args: keyword call arguments])
 _MODES = {
     "create_dataset": ("create_dataset", "create_dataset", [
         (("audio_path",), dict(type=str, help="can be /path/to/*.wav")),
         (("-o", "--output-dir"), dict(type=str, required=True, help="The folder where the tensor files will be saved")),
-    ], lambda a: (a.audio_path, a.output_dir)),
+        (("--resample",), dict(action="store_true", help="resample files that are not at 44.1 kHz (else they are refused)")),
+    ], lambda a: (a.audio_path, a.output_dir), lambda a: {"resample": True} if a.resample else {}),
     "train": ("train", "train", [
         (("run",), dict(type=str, metavar="RUN_NAME")),
         (("-o", "--out-path"), dict(dest="out_path", type=str, required=True)),
@@ -33,7 +34,7 @@ def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser("MusicGAN")
     modes = parser.add_subparsers(dest="mode")
     modes.required = True
-    for mode, (_, _, arguments, _) in _MODES.items():
+    for mode, (_, _, arguments, *_) in _MODES.items():
         sub = modes.add_parser(mode)
         for flags, kwargs in arguments:
             sub.add_argument(*flags, **kwargs)
@@ -42,8 +43,9 @@ def build_parser() -> argparse.ArgumentParser:
 
 def main(argv=None) -> None:
     args = build_parser().parse_args(argv)
-    module, function, _, call_args = _MODES[args.mode]
-    getattr(importlib.import_module(f".{module}", __package__), function)(*call_args(args))
+    module, function, _, call_args, *call_kwargs = _MODES[args.mode]
+    kwargs = call_kwargs[0](args) if call_kwargs else {}
+    getattr(importlib.import_module(f".{module}", __package__), function)(*call_args(args), **kwargs)
 
 
 if __name__ == "__main__":

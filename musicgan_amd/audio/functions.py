@@ -56,21 +56,59 @@ def stft_from_waveform(raw_audio: th.Tensor, nperseg: int = constant.N_FFT, stri
     return ops.stft_1024(mono) if fast else ops.stft_generic(mono, nperseg, stride)
 
 
-def stft_from_pcm(pcm: th.Tensor, nperseg: int = constant.N_FFT, stride: int = constant.STFT_STRIDE) -> th.Tensor:
+def resample(waveform: th.Tensor, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99,
+             resampling_method: str = "sinc_interp_hann", beta=None) -> th.Tensor:
+    """torchaudio.functional.resample: (..., time) -> (..., ceil(time * new / orig)) (rates reduced by their gcd), rows
+    independent, band-limited sinc interpolation with a Hann window (`mg_resample_pcm`, one launch).  Results are float32 on the
+    device; a CPU tensor is moved there first.  orig_freq == new_freq returns `waveform` itself, as torchaudio does.
+    Only sinc_interp_hann is built (`beta` belongs to the Kaiser window and is ignored, as torchaudio ignores it for Hann)."""
+    for name, f in (("orig_freq", orig_freq), ("new_freq", new_freq)):
+        if isinstance(f, bool) or not isinstance(f, (int, float)) or int(f) != f or f <= 0:
+            raise ValueError(f"{name} must be a positive integer, got {f!r}")
+    if int(lowpass_filter_width) != lowpass_filter_width or lowpass_filter_width <= 0:
+        raise ValueError(f"lowpass_filter_width must be a positive integer, got {lowpass_filter_width!r}")
+    if not rolloff > 0:
+        raise ValueError(f"rolloff must be positive, got {rolloff!r}")
+    if resampling_method != "sinc_interp_hann":
+        raise ValueError(f"resampling_method {resampling_method!r} is not supported: only 'sinc_interp_hann' is built")
+    orig_freq, new_freq = int(orig_freq), int(new_freq)
+    if orig_freq == new_freq:
+        return waveform
+    if not waveform.is_floating_point():
+        raise ValueError(f"resample expects a floating-point waveform, got {waveform.dtype}")
+    dev = waveform.device if waveform.is_cuda else _device()
+    lead, length = waveform.shape[:-1], waveform.shape[-1]
+    out_len = ops.resample_len(length, orig_freq, new_freq)
+    if waveform.numel() == 0:
+        return th.zeros((*lead, out_len), dtype=th.float32, device=dev)
+    x = waveform.to(dev, th.float32).reshape(-1, length)
+    if length > 1 and x.stride(1) != 1:
+        x = x.contiguous()
+    return ops.resample_rows(x, orig_freq, new_freq, int(lowpass_filter_width), float(rolloff)).reshape(*lead, out_len)
+
+
+def stft_from_pcm(pcm: th.Tensor, nperseg: int = constant.N_FFT, stride: int = constant.STFT_STRIDE,
+                  sample_rate: int = constant.SAMPLE_RATE) -> th.Tensor:
     """PCM frames (frames, channels) exactly as a WAV file stores them (wavio.load_pcm), on the device -> the same result as
-    wav_to_stft on that file: normalisation to [-1, 1], mono mean and STFT in one launch (two for other window sizes)."""
+    wav_to_stft on that file: normalisation to [-1, 1], mono mean and STFT in one launch (two for other window sizes).
+    `sample_rate` other than 44.1 kHz: normalisation, mono mean and the resampling to 44.1 kHz in one launch, then the STFT."""
+    if sample_rate != constant.SAMPLE_RATE:
+        mono = ops.resample_pcm(pcm, sample_rate, constant.SAMPLE_RATE)
+        return ops.stft_1024(mono) if _fast_stft(nperseg, stride) else ops.stft_generic(mono, nperseg, stride)
     if _fast_stft(nperseg, stride):
         return ops.stft_1024_pcm(pcm)
     return ops.stft_generic(ops.pcm_to_mono(pcm), nperseg, stride)
 
 
-def wav_to_stft(wav_p: str, nperseg: int = constant.N_FFT, stride: int = constant.STFT_STRIDE) -> th.Tensor:
+def wav_to_stft(wav_p: str, nperseg: int = constant.N_FFT, stride: int = constant.STFT_STRIDE, *, resample: bool = False) -> th.Tensor:
+    """`resample`: a file at any other rate is resampled to 44.1 kHz first (torchaudio.functional.resample's defaults); without
+    it such a file raises, as the reference does.  A 44.1 kHz file takes the same path either way."""
     pcm, sr = wavio.load_pcm(wav_p)
-    assert sr == constant.SAMPLE_RATE, \
+    assert resample or sr == constant.SAMPLE_RATE, \
         f"Audio sample rate must be {constant.SAMPLE_RATE}Hz, " \
         f"file \"{wav_p}\" is {sr}Hz"
     import numpy as np
-    return stft_from_pcm(th.from_numpy(np.ascontiguousarray(pcm)).to(_device()), nperseg, stride)
+    return stft_from_pcm(th.from_numpy(np.ascontiguousarray(pcm)).to(_device()), nperseg, stride, sample_rate=sr)
 
 
 def stft_to_phase_magn(complex_values: th.Tensor, nb_vec: int = constant.N_VEC) -> Tuple[th.Tensor, th.Tensor]:

@@ -10,6 +10,9 @@ leave behind (201 samples x 4 MiB, create_dataset.py:52-62).  So the loop is a p
 float64 and `th.save`s it while the GPU and the copy engine work on the next chunk / file, and the float32 side-car of the fast
 loader (audio/dataset.py) is streamed out of the same pinned chunks instead of re-reading every `.pt` afterwards.
 `stats` (optional dict) receives where the time went: bench.py's `create_dataset_e2e` record.
+`resample=True` accepts files at any sample rate: their PCM is resampled to 44.1 kHz on the device (ops.resample_pcm, the
+torchaudio.functional.resample a user of the reference calls first) in the launch that also normalises it; 44.1 kHz files take the
+unchanged path.
 """
 import glob
 import json
@@ -250,10 +253,10 @@ class _Chunk:
 
 
 def create_dataset(audio_path: str, dataset_output_dir: str, *, packed: bool = True, writer_threads: int = 0,
-                   stats: dict = None) -> None:
+                   stats: dict = None, resample: bool = False) -> None:
     """`packed` (extension, single-process runs): also write the float32 memory-mapped side-car the fast loader reads
     (audio/dataset.py); the reference-format `magn_phase_{idx}.pt` files are written either way.  `writer_threads`: 0 = one per
-    available CPU (at most 16)."""
+    available CPU (at most 16).  `resample`: files not at 44.1 kHz are resampled to it (else they raise, as in the reference)."""
     w_p = glob.glob(audio_path)
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:
@@ -269,8 +272,12 @@ def create_dataset(audio_path: str, dataset_output_dir: str, *, packed: bool = T
         th.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
         counts = []
         for p in w_p:
-            data, _ = audio.wavio.load_pcm(p)
-            counts.append(_nb_samples(data.shape[0], nb_vec))
+            data, sr = audio.wavio.load_pcm(p)
+            frames = data.shape[0]
+            if resample and sr != audio.SAMPLE_RATE:  # the samples come from the resampled signal: ceil(44100 L / sr) frames
+                from . import ops
+                frames = ops.resample_len(frames, sr, audio.SAMPLE_RATE)
+            counts.append(_nb_samples(frames, nb_vec))
     t_setup = time.perf_counter()
     mine = [f_i for f_i in range(len(w_p)) if world == 1 or f_i % world == rank]
     first_idx = {}
@@ -324,12 +331,12 @@ def create_dataset(audio_path: str, dataset_output_dir: str, *, packed: bool = T
             if world > 1:
                 idx = first_idx[f_i]
             t0 = time.perf_counter()
-            assert sr == audio.SAMPLE_RATE, \
+            assert resample or sr == audio.SAMPLE_RATE, \
                 f"Audio sample rate must be {audio.SAMPLE_RATE}Hz, " \
                 f"file \"{wav_p}\" is {sr}Hz"
             th.cuda.current_stream().wait_event(ready)  # the upload (loader's stream) is ordered in front of the STFT
             pcm.record_stream(th.cuda.current_stream())
-            complex_values = audio.functions.stft_from_pcm(pcm, nperseg=audio.N_FFT, stride=audio.STFT_STRIDE)
+            complex_values = audio.functions.stft_from_pcm(pcm, nperseg=audio.N_FFT, stride=audio.STFT_STRIDE, sample_rate=sr)
             del pcm
             t1 = time.perf_counter()
             t_load += t1 - t0

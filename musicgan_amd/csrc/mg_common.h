@@ -91,3 +91,36 @@ __device__ __forceinline__ unsigned mg_pos_bit(float v) {
   return (unsigned)(b < 0 ? 0 : (b > 1 ? 1 : b));
 }
 __device__ __forceinline__ float mg_lrelu_mask(float act, float slope) { return act > 0.f ? 1.f : slope; }
+
+// One mono sample of PCM frames as a WAV file stores them (MG_PCM_* kinds): every channel scaled to [-1, 1] as
+// torchaudio.load(normalize=True) does (int16: / 32768, int32: / 2^31, uint8: (v - 128) / 128), then the mean over channels
+// [functions.py:43-49: raw_audio.mean(0)] accumulated in channel order.  mg_pcm_to_mono and mg_resample_pcm both load through it,
+// so the resampler's mono input is bit for bit what mg_pcm_to_mono writes.  KIND / CH >= 0 fix the kind / channel count at compile
+// time (the same operations in the same order: only the branches go, so that a caller can keep several loads in flight);
+// two float32 / int16 channels are read as one 8- / 4-byte load (frames start aligned to their size, as every caller's buffers do).
+__device__ __forceinline__ float mg_pcm_norm(const void* __restrict__ p, long long e, int kind) {
+  if (kind == MG_PCM_F32) return reinterpret_cast<const float*>(p)[e];
+  if (kind == MG_PCM_I16) return (float)reinterpret_cast<const short*>(p)[e] / 32768.0f;
+  if (kind == MG_PCM_I32) return (float)reinterpret_cast<const int*>(p)[e] / 2147483648.0f;
+  return ((float)reinterpret_cast<const unsigned char*>(p)[e] - 128.0f) / 128.0f;
+}
+template <int KIND = -1, int CH = 0>
+__device__ __forceinline__ float mg_pcm_mono_t(const void* __restrict__ pcm, long long frame, int C, int kind) {
+  const int nc = CH > 0 ? CH : C;
+  float s = 0.f;
+  if constexpr (CH == 2 && KIND == MG_PCM_I16) {
+    const short2 v = reinterpret_cast<const short2*>(pcm)[frame];
+    s += (float)v.x / 32768.0f;
+    s += (float)v.y / 32768.0f;
+  } else if constexpr (CH == 2 && KIND == MG_PCM_F32) {
+    const float2 v = reinterpret_cast<const float2*>(pcm)[frame];
+    s += v.x;
+    s += v.y;
+  } else {
+    for (int c = 0; c < nc; ++c) s += mg_pcm_norm(pcm, frame * nc + c, KIND >= 0 ? KIND : kind);
+  }
+  return nc > 1 ? s / (float)nc : s;
+}
+__device__ __forceinline__ float mg_pcm_mono(const void* __restrict__ pcm, long long frame, int C, int kind) {
+  return mg_pcm_mono_t<>(pcm, frame, C, kind);
+}

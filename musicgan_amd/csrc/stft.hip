@@ -302,19 +302,7 @@ __global__ void __launch_bounds__(64 * NWAVE, 2) stft1024_kernel(const void* __r
 
 // Other sample formats / channel counts: one pass to mono float32 first (rare: 8-bit, 32-bit integer, more than two channels).
 __global__ void __launch_bounds__(256) pcm_to_mono_k(const void* __restrict__ pcm, float* __restrict__ mono, long long L, int C, int kind) {
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < L; i += (long long)gridDim.x * 256) {
-    float s = 0.f;
-    for (int c = 0; c < C; ++c) {
-      const long long e = i * C + c;
-      float v;
-      if (kind == MG_PCM_F32) v = reinterpret_cast<const float*>(pcm)[e];
-      else if (kind == MG_PCM_I16) v = (float)reinterpret_cast<const short*>(pcm)[e] / 32768.0f;
-      else if (kind == MG_PCM_I32) v = (float)reinterpret_cast<const int*>(pcm)[e] / 2147483648.0f;
-      else v = ((float)reinterpret_cast<const unsigned char*>(pcm)[e] - 128.0f) / 128.0f;
-      s += v;
-    }
-    mono[i] = C > 1 ? s / (float)C : s;
-  }
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < L; i += (long long)gridDim.x * 256) mono[i] = mg_pcm_mono(pcm, i, C, kind);
 }
 
 template <int PCM, int CH>

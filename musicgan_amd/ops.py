@@ -1042,6 +1042,74 @@ def pcm_to_mono(pcm: torch.Tensor) -> torch.Tensor:
     return mono
 
 
+def resample_len(length: int, orig_freq: int, new_freq: int) -> int:
+    """ceil(n * length / o), o / n = orig_freq / new_freq reduced: the length torchaudio.functional.resample returns (host only)."""
+    out = _lib.load().mg_resample_len(int(length), int(orig_freq), int(new_freq))
+    if out < 0:
+        raise ValueError(f"resample_len: bad arguments ({length}, {orig_freq}, {new_freq})")
+    return out
+
+
+def resample_bank_host(orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99):
+    """The compact polyphase bank on the host (no GPU needed): (taps float32 [phases, 2w + 1], start int32 [phases]) -- compact
+    tap j of phase p is tap start[p] + j of row p of torchaudio's kernel."""
+    lib = _lib.load()
+    phases, taps = ctypes.c_int(0), ctypes.c_int(0)
+    nbytes = lib.mg_resample_bank_size(int(orig_freq), int(new_freq), int(lowpass_filter_width), float(rolloff),
+                                       ctypes.byref(phases), ctypes.byref(taps))
+    if nbytes == 0:
+        raise ValueError(f"resample bank: bad arguments ({orig_freq}, {new_freq}, {lowpass_filter_width}, {rolloff})")
+    raw = torch.empty(nbytes, dtype=torch.uint8)
+    check(lib.mg_resample_bank(int(orig_freq), int(new_freq), int(lowpass_filter_width), float(rolloff), _p(raw), nbytes),
+          "mg_resample_bank")
+    n, t = phases.value, taps.value
+    return raw[:4 * n * t].view(torch.float32).view(n, t), raw[4 * n * t:].view(torch.int32)
+
+
+_resample_banks = {}
+
+
+def resample_bank(orig_freq: int, new_freq: int, lowpass_filter_width: int, rolloff: float, device) -> torch.Tensor:
+    """mg_resample_bank's bytes on `device`, built once per (reduced rates, width, rolloff, device)."""
+    import math
+    g = math.gcd(int(orig_freq), int(new_freq))
+    key = (int(orig_freq) // g, int(new_freq) // g, int(lowpass_filter_width), float(rolloff), str(device))
+    if key not in _resample_banks:
+        taps, start = resample_bank_host(key[0], key[1], key[2], key[3])
+        raw = torch.cat([taps.reshape(-1).view(torch.uint8), start.view(torch.uint8)])
+        _resample_banks[key] = raw.to(device)
+    return _resample_banks[key]
+
+
+def _resample(src: torch.Tensor, kind: int, channels: int, rows: int, row_stride: int, length: int, orig_freq: int, new_freq: int,
+              lowpass_filter_width: int, rolloff: float) -> torch.Tensor:
+    bank = resample_bank(orig_freq, new_freq, lowpass_filter_width, rolloff, src.device)
+    out = torch.empty((rows, resample_len(length, orig_freq, new_freq)), dtype=torch.float32, device=src.device)
+    check(_lib.load().mg_resample_pcm(_p(src), kind, channels, rows, row_stride, length, int(orig_freq), int(new_freq),
+                                      int(lowpass_filter_width), float(rolloff), _p(bank), bank.numel(), _p(out), _s()),
+          "mg_resample_pcm")
+    return out
+
+
+def resample_pcm(pcm: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99) -> torch.Tensor:
+    """PCM frames (L, C) / (L,) as stored (float32 / int16 / int32 / uint8), on the device -> mono float32 [ceil(n L / o)] at
+    new_freq: the normalisation and mono mean of pcm_to_mono (the same bits) and torchaudio.functional.resample in one launch."""
+    if not pcm.is_cuda or not pcm.is_contiguous() or pcm.dtype not in _PCM_KIND:
+        raise _lib.MusicGanHipError(f"resample_pcm: contiguous GPU tensor of float32 / int16 / int32 / uint8 expected, got {pcm.dtype}")
+    length, ch = pcm.shape[0], (pcm.shape[1] if pcm.dim() == 2 else 1)
+    if int(orig_freq) == int(new_freq):
+        return pcm_to_mono(pcm)
+    return _resample(pcm, _PCM_KIND[pcm.dtype], ch, 1, length, length, orig_freq, new_freq, lowpass_filter_width, rolloff)[0]
+
+
+def resample_rows(x: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99) -> torch.Tensor:
+    """float32 (rows, L) on the device, unit stride along L (any row stride) -> (rows, ceil(n L / o)), rows independent."""
+    if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or (x.shape[1] > 1 and x.stride(1) != 1):
+        raise _lib.MusicGanHipError("resample_rows: float32 (rows, L) GPU tensor with unit stride along L expected")
+    rows, length = x.shape
+    return _resample(x, _lib.MG_PCM_F32, 1, rows, x.stride(0), length, orig_freq, new_freq, lowpass_filter_width, rolloff)
+
+
 def stft_generic(wav_mono: torch.Tensor, n_fft: int, hop: int) -> torch.Tensor:
     """mono fp32 [L] -> complex64 [n_fft/2, 1 + L//hop] for any power-of-two n_fft in [64, 8192] (untuned path)."""
     _chk(wav_mono)
