@@ -283,10 +283,11 @@ def _oracle_full_step(level, batch):
     return _ORACLE_CACHE[key]
 
 
-@pytest.mark.parametrize("level,batch", [(5, 2), (4, 32), (6, 1), (7, 1), (5, 16), (3, 8), (6, 6)])
+@pytest.mark.parametrize("level,batch", [(5, 2), (4, 32), (6, 1), (7, 1), (5, 16), (3, 8), (6, 6), (5, 64)])
 def test_full_size_step_against_fp64_oracle(level, batch, conv_mode):
     """BASELINE.json's shapes against the ORACLE (not against another HIP path): the headline level 5 (2x128x128; batch 2 -- the
-    critic then runs on 6 images, every kernel on the tiling it uses at batch 64 -- and batch 16: 48 images through the critic),
+    critic then runs on 6 images, every kernel on the tiling it uses at batch 64 -- batch 16: 48 images through the critic, and
+    batch 64 itself: the benchmark's step, 192 images through the critic),
     configs[1] in full (level 4, 2x64x64, batch 32), and the levels the reference trains at (6 and 7, 2x256x256 / 2x512x512,
     one image: the few-channel tilings that only exist there -- wino3x3_mfma<1,1,2> / <1,3,2>, wino3x3_strip, the narrow
     weight-gradient kernels; reference shapes generator.py:67-76, discriminator.py:60-70), through the product's training path -- ProGANStepper's fused critic step and its generator step: generated
@@ -380,39 +381,90 @@ def test_full_size_step_is_algorithm_independent(monkeypatch, level, batch):
     versus the direct implicit-GEMM kernels (validated against the oracle at the small sizes above).  The two paths share no
     multiply order, so agreement to fp32 round-off at full size checks indexing, tiling, halo handling and split-K at the sizes
     the benchmark runs.  Levels 6 and 7 (256 x 256 and the final 512 x 512 maps, odd batch) cover the last two growth
-    steps of a full training run, which no fixture reaches."""
+    steps of a full training run, which no fixture reaches.
+
+    The "direct" side switches off every route that has a switch (DIRECT_ROUTING): Winograd forward / data gradient / weight
+    gradient, the 9-component up-sampling kernels and the sub-pixel data gradient, the fused generator head (forward epilogue and
+    backward), the single-launch fade-in ends, the small-map and PixelNorm-staging convolutions, tile masks, the 1x1-map weight
+    gradient, and every conv + PixelNorm fusion (MG_PN_FUSE_MIN_PIXELS beyond any map).  A routing census (tests/routing_census.py)
+    of both sides asserts that this holds: the product side really launches the kernels of PRODUCT_ONLY at the headline size and
+    the direct side launches none of them nor any Winograd-packed conv.  What has no switch runs on both sides and is checked
+    launch by launch at the headline shapes against float64 in test_headline_shapes_gpu.py: the direct implicit-GEMM conv3x3 (the
+    product side's 1x1 maps and its up-sampling conv of 4x4 maps), PixelNorm forward and backward, up-sampling backward,
+    AvgPool2d backward, the LeakyReLU backward, the classifier (linear1_fwd / linear1_bwd), the penalty's interpolation and
+    per-sample sums, the stems' 1x1 weight gradient and the score means."""
+    import bench
+    from routing_census import census
+
+    side = bench.LEVEL_SIDE[level]
+    grads, terms, launched = {}, {}, {}
+    monkeypatch.setenv("MG_GRAPHS", "0")  # every launch eager: the census sees all of them
+    for mode in ("product", "direct"):
+        if mode == "direct":
+            for k, v in DIRECT_ROUTING.items():
+                monkeypatch.setenv(k, v)
+        with census() as c:
+            grads[mode], terms[mode] = _one_full_size_step(level, batch, side)
+        launched[mode] = c
+    # (a) the product side runs the fused and Winograd kernels at the headline size -- a routing change that stops sending work
+    # to one of them must not leave this comparison vacuous; (b) the direct side runs none of them
+    prod, direct = launched["product"].ops(), launched["direct"].ops()
+    wino_conv = lambda c: [r for r in c.of("conv3x3") if dict(r[1]).get("wino") is not None] + c.of("conv3x3_fade")
+    if (level, batch) == (5, 64):
+        for alts in PRODUCT_ONLY_AT_HEADLINE:
+            assert prod & set(alts), f"the product side no longer launches {' / '.join(alts)} at level 5 batch 64"
+        assert wino_conv(launched["product"]), "the product side no longer launches a Winograd conv3x3"
+    assert not direct & set(PRODUCT_ONLY), f"the direct side still launches {sorted(direct & set(PRODUCT_ONLY))}"
+    assert not wino_conv(launched["direct"]), "the direct side still launches a Winograd-packed conv3x3"
+    _compare_full_size_steps(grads, terms)
+
+
+# Every route with an off switch, switched off (test_full_size_step_is_algorithm_independent's "direct" side)
+DIRECT_ROUTING = {"MG_WINO": "0", "MG_WINO_WGRAD": "0", "MG_UPCONV_DGRAD": "0", "MG_WINOUPS": "0", "MG_HEAD_FUSE": "0",
+                  "MG_FUSE_ENDS": "0", "MG_SMALLCONV": "0", "MG_PN_STAGED": "0", "MG_TILEMASK": "0", "MG_WGRAD_1X1MAP": "0",
+                  "MG_PN_FUSE_MIN_PIXELS": str(1 << 62)}
+# the kernels only the product side may launch
+PRODUCT_ONLY = ("winoups3x3", "winoups3x3_head", "winoups3x3_dgrad", "winoups3x3_dgrad_pn", "upconv3x3", "upconv3x3_dgrad",
+                "gen_head_bwd", "stem_pair", "stem_pair_gx", "head_pair", "head_pair_from_mp", "blend_up_bwd", "conv3x3_fade",
+                "conv3x3_small", "conv3x3_small_pn", "gp_apply", "upsample2x_fwd")
+# ... of which the product side must launch these (alternatives: the same kernel family) at level 5 batch 64.  The plain 9-component
+# forward (winoups3x3) has no layer there -- the 80-channel up-sampling layer takes the sub-pixel kernel, the last one the head
+# epilogue form -- and with the generator's head in that epilogue the fade-in pair starts from its result (head_pair_from_mp).
+PRODUCT_ONLY_AT_HEADLINE = (("winoups3x3_head",), ("winoups3x3_dgrad", "winoups3x3_dgrad_pn"),
+                            ("gen_head_bwd",), ("stem_pair",), ("stem_pair_gx",), ("head_pair", "head_pair_from_mp"),
+                            ("conv3x3_fade",), ("conv3x3_small",), ("upconv3x3",))
+
+
+def _one_full_size_step(level, batch, side):
+    """One D step and one G step of fresh level-`level` nets on fixed data: (({D./G. gradients}, disc loss, penalty, gen loss),
+    {un-cancelled critic terms})."""
     import bench
     from musicgan_amd.optim import FusedAdam
     from musicgan_amd.train_step import ProGANStepper
+    gen, disc = bench.build_nets(level, 32, DEV)
+    og = FusedAdam(gen.parameters(), lr=1e-3, betas=(0.0, 0.9))
+    od = FusedAdam(disc.parameters(), lr=1e-3, betas=(0.0, 0.9))
+    od.step = lambda *a, **k: None  # keep the gradients observable: no update
+    og.step = lambda *a, **k: None
+    st = ProGANStepper(gen, disc, og, od, 32)
+    rng = torch.Generator(device=DEV).manual_seed(1234)
+    x_real = torch.rand(batch, 2, side, side, device=DEV, generator=rng) * 2 - 1
+    z = torch.randn(batch, 32, 2, 2, device=DEV, generator=rng)
+    eps = torch.rand(batch, 1, 1, 1, device=DEV, generator=rng)
+    md = st.d_step(x_real, 0.5, z=z, eps=eps)
+    gd = {"D." + k: p.grad.detach().clone() for k, p in disc.named_parameters() if p.grad is not None}
+    mg = st.g_step(batch, 0.5, DEV, z=z)
+    gg = {"G." + k: p.grad.detach().clone() for k, p in gen.named_parameters() if p.grad is not None}
+    # un-cancelled scale of every critic gradient: d mean(D(x_real)) / dw alone.  At init the real and fake terms of the
+    # Wasserstein loss nearly cancel in the deep blocks (own max 7e-9 against terms of 3e-3 at level 6), so fp32 round-off
+    # of the TERMS -- measured 1e-7 of them -- is the floor of any comparison of the residue.
+    disc.zero_grad()
+    disc(x_real, 0.5).mean().backward()
+    terms = {"D." + k: p.grad.detach().clone() for k, p in disc.named_parameters() if p.grad is not None}
+    return ({**gd, **gg}, float(md["disc_loss"]), float(md["grad_pen"]), float(mg["gen_loss"])), terms
 
-    side = bench.LEVEL_SIDE[level]
-    grads, terms = {}, {}
-    for mode in ("product", "direct"):
-        if mode == "direct":
-            monkeypatch.setenv("MG_WINO", "0")
-            monkeypatch.setenv("MG_WINO_WGRAD", "0")
-            monkeypatch.setenv("MG_UPCONV_DGRAD", "0")
-        gen, disc = bench.build_nets(level, 32, DEV)
-        og = FusedAdam(gen.parameters(), lr=1e-3, betas=(0.0, 0.9))
-        od = FusedAdam(disc.parameters(), lr=1e-3, betas=(0.0, 0.9))
-        od.step = lambda *a, **k: None  # keep the gradients observable: no update
-        og.step = lambda *a, **k: None
-        st = ProGANStepper(gen, disc, og, od, 32)
-        rng = torch.Generator(device=DEV).manual_seed(1234)
-        x_real = torch.rand(batch, 2, side, side, device=DEV, generator=rng) * 2 - 1
-        z = torch.randn(batch, 32, 2, 2, device=DEV, generator=rng)
-        eps = torch.rand(batch, 1, 1, 1, device=DEV, generator=rng)
-        md = st.d_step(x_real, 0.5, z=z, eps=eps)
-        gd = {"D." + k: p.grad.detach().clone() for k, p in disc.named_parameters() if p.grad is not None}
-        mg = st.g_step(batch, 0.5, DEV, z=z)
-        gg = {"G." + k: p.grad.detach().clone() for k, p in gen.named_parameters() if p.grad is not None}
-        # un-cancelled scale of every critic gradient: d mean(D(x_real)) / dw alone.  At init the real and fake terms of the
-        # Wasserstein loss nearly cancel in the deep blocks (own max 7e-9 against terms of 3e-3 at level 6), so fp32 round-off
-        # of the TERMS -- measured 1e-7 of them -- is the floor of any comparison of the residue.
-        disc.zero_grad()
-        disc(x_real, 0.5).mean().backward()
-        terms[mode] = {"D." + k: p.grad.detach().clone() for k, p in disc.named_parameters() if p.grad is not None}
-        grads[mode] = ({**gd, **gg}, float(md["disc_loss"]), float(md["grad_pen"]), float(mg["gen_loss"]))
+
+def _compare_full_size_steps(grads, terms):
     (ga, la, pa, qa), (gb, lb, pb, qb) = grads["product"], grads["direct"]
     for k, t in terms["direct"].items():
         assert maxabs_err(terms["product"][k], t) <= 2e-4 * float(t.abs().max()), k
