@@ -383,6 +383,35 @@ int mg_resample_bank(int orig_freq, int new_freq, int lowpass_filter_width, doub
 int mg_resample_pcm(const void* pcm, int kind, int channels, int rows, int64_t row_stride, int64_t L, int orig_freq, int new_freq,
                     int lowpass_filter_width, double rolloff, const void* bank, size_t bank_bytes, float* out, mg_stream_t stream);
 
+/* ------------------------------------------------------------------ FLAC decoding [torchaudio.load of a .flac file: functions.py:43,
+ * th_audio.load]
+ * RFC 9639 streams of 1-8 channels, 4-24 bits, any block size, fixed or variable blocking.  The host parses the metadata blocks and
+ * passes the AUDIO REGION (the bytes from the first frame header to the end of the stream) as a device buffer that is 16-byte aligned
+ * and readable, zero filled past nbytes, up to mg_flac_padded_bytes(nbytes).  Offsets below are bytes into that region.
+ * Workspace (mg_flac_ws_bytes, for at most cand_cap frame-header candidates) starts with int64 status[16]:
+ *   [0] candidates found (more than cand_cap: nothing was decoded, call again with a larger cap), [1] frames, [2] samples,
+ *   [3] chain error (0 ok, 1 no valid header where frame [4] must start, at byte [5]; 3 candidates over cap), [6] blocking,
+ *   [7] first frame with a problem (INT64_MAX: none), [8] its MG_FLAC_F* flags, [9] its start, [10] its decoded end (after the
+ *   CRC-16), [11] the next frame's start in the chain.
+ * Host-only size queries: */
+#define MG_FLAC_F_CRC 1    /* the CRC-16 of the frame as decoded does not check */
+#define MG_FLAC_F_END 2    /* the decoded end is not where the chain put the next frame (a false sync code was taken) */
+#define MG_FLAC_F_HDR 4    /* header rate / depth / channels disagree with STREAMINFO */
+#define MG_FLAC_F_SYNTAX 8 /* invalid subframe fields, or the frame runs past the region */
+#define MG_FLAC_F_RANGE 16 /* samples beyond out_frames */
+size_t mg_flac_padded_bytes(int64_t nbytes);
+size_t mg_flac_ws_bytes(int64_t nbytes, int64_t cand_cap);
+/* frame-header scan of every byte offset (sync code, fields, CRC-8), candidates in offset order, and the frame chain from byte 0 */
+int mg_flac_scan(const void* data, int64_t nbytes, void* ws, size_t ws_bytes, int64_t cand_cap, mg_stream_t stream);
+/* keeps frames 0 .. frame - 1 and chains again from a header at byte `offset` (the decoded end of frame - 1) */
+int mg_flac_rechain(const void* data, int64_t nbytes, void* ws, size_t ws_bytes, int64_t cand_cap, int64_t frame, int64_t offset,
+                    mg_stream_t stream);
+/* decodes the chained frames into out (out_frames, channels): int16 (bits <= 16) or int32, samples left-justified in the container
+ * (v << (16 - bits) or v << (32 - bits)), as wav / aiff PCM is stored; planar: int32 [channels][out_frames] scratch.  channels,
+ * bits and sample_rate come from STREAMINFO and are checked against every frame header. */
+int mg_flac_decode(const void* data, int64_t nbytes, void* ws, size_t ws_bytes, int64_t cand_cap, int channels, int bits,
+                   int sample_rate, int32_t* planar, void* out, int64_t out_frames, mg_stream_t stream);
+
 /* ------------------------------------------------------------------ multi-layer chains on small maps
  * The <= 4x4 ends of both networks -- the generator's first blocks [generator.py:15-40,67-76: conv3x3 -> LeakyReLU -> PixelNorm
  * -> Upsample -> conv3x3 -> LeakyReLU -> PixelNorm] and the critic's last blocks + classifier [discriminator.py:14-34,60-70,

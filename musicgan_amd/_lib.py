@@ -157,6 +157,11 @@ SIGNATURES = {
     "mg_resample_bank_size": (c_size_t, [c_int, c_int, c_int, ctypes.c_double, POINTER(c_int), POINTER(c_int)]),
     "mg_resample_bank": (c_int, [c_int, c_int, c_int, ctypes.c_double, _P, c_size_t]),
     "mg_resample_pcm": (c_int, [_P, c_int, c_int, c_int, c_int64, c_int64, c_int, c_int, c_int, ctypes.c_double, _P, c_size_t, _P, _P]),
+    "mg_flac_padded_bytes": (c_size_t, [c_int64]),
+    "mg_flac_ws_bytes": (c_size_t, [c_int64, c_int64]),
+    "mg_flac_scan": (c_int, [_P, c_int64, _P, c_size_t, c_int64, _P]),
+    "mg_flac_rechain": (c_int, [_P, c_int64, _P, c_size_t, c_int64, c_int64, c_int64, _P]),
+    "mg_flac_decode": (c_int, [_P, c_int64, _P, c_size_t, c_int64, c_int, c_int, c_int, _P, _P, c_int64, _P]),
     "mg_crc32_f64_ws_bytes": (c_size_t, [c_int, c_int64]),
     "mg_crc32_f64": (c_int, [_P, _P, _P, c_size_t, c_int, c_int64, _P]),
     "mg_pt_write_samples": (c_int, [_P, c_int, c_int64, ctypes.c_char_p, ctypes.c_char_p, c_int64, ctypes.c_char_p, c_int64, c_int, c_int64]),

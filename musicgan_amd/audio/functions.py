@@ -103,10 +103,17 @@ def stft_from_pcm(pcm: th.Tensor, nperseg: int = constant.N_FFT, stride: int = c
 def wav_to_stft(wav_p: str, nperseg: int = constant.N_FFT, stride: int = constant.STFT_STRIDE, *, resample: bool = False) -> th.Tensor:
     """`resample`: a file at any other rate is resampled to 44.1 kHz first (torchaudio.functional.resample's defaults); without
     it such a file raises, as the reference does.  A 44.1 kHz file takes the same path either way."""
-    pcm, sr = wavio.load_pcm(wav_p)
+    import os
+    if os.path.splitext(wav_p)[1].lower() == ".flac":  # decoded on the device: the PCM never visits the host
+        sr = wavio.flac.read_header(wav_p).sample_rate
+        pcm = None
+    else:
+        pcm, sr = wavio.load_pcm(wav_p)
     assert resample or sr == constant.SAMPLE_RATE, \
         f"Audio sample rate must be {constant.SAMPLE_RATE}Hz, " \
         f"file \"{wav_p}\" is {sr}Hz"
+    if pcm is None:
+        return stft_from_pcm(wavio.load_pcm_device(wav_p, _device()), nperseg, stride, sample_rate=sr)
     import numpy as np
     return stft_from_pcm(th.from_numpy(np.ascontiguousarray(pcm)).to(_device()), nperseg, stride, sample_rate=sr)
 

@@ -1,7 +1,8 @@
 """Minimal audio file IO (the reference uses torchaudio.load/save, functions.py:43,139; torchaudio is not a dependency here).
 load() mirrors torchaudio.load(normalize=True): float32 tensor (channels, samples) in [-1, 1] and the sample rate.
 Containers: RIFF WAV (scipy), AIFF / AIFF-C and Sun AU with linear PCM (Python's standard library) -- the uncompressed formats
-torchaudio's backends read without a codec; compressed formats (flac, mp3, ogg) need decoders this image does not have and raise."""
+torchaudio's backends read without a codec -- and FLAC, whose frames are decoded on the GPU (ops.flac_decode; there is no CPU
+decoder, so reading FLAC without a GPU raises MusicGanHipError).  mp3 and ogg raise."""
 from __future__ import annotations
 
 import os
@@ -9,6 +10,8 @@ import os
 import numpy as np
 import torch
 from scipy.io import wavfile
+
+from . import flac
 
 
 def _linear_pcm(raw: bytes, width: int, channels: int, what: str) -> np.ndarray:
@@ -47,9 +50,11 @@ def _read_frames(path: str, mmap: bool = False):
                 raise ValueError(f"{path}: {f.getcompname()} AU files are not supported (linear PCM only)")
             raw, width, ch, sr = f.readframes(f.getnframes()), f.getsampwidth(), f.getnchannels(), f.getframerate()
         return _linear_pcm(raw, width, ch, path), int(sr)
+    if ext == ".flac":
+        return load_pcm_device(path).cpu().numpy(), flac.read_header(path).sample_rate
     if ext not in (".wav", ".wave", ""):
-        raise ValueError(f"{path}: only WAV, AIFF and AU (linear PCM) files can be read here; torchaudio's codec-backed formats "
-                         f"(flac, mp3, ogg, ...) need a decoder this build does not ship")
+        raise ValueError(f"{path}: only WAV, AIFF, AU (linear PCM) and FLAC files can be read here; torchaudio's other "
+                         f"codec-backed formats (mp3, ogg, ...) need a decoder this build does not ship")
     try:
         sr, data = wavfile.read(path, mmap=mmap)
     except ValueError:  # formats scipy cannot map (e.g. 24-bit)
@@ -75,7 +80,9 @@ def load(path: str):
 def load_pcm(path: str, mmap: bool = True):
     """The file's frames as stored: array (frames, channels) of int16 / int32 / uint8 / float32 (a read-only memory map where the
     format allows) and the sample rate -- what `load` normalises and transposes; the device path does both inside the STFT kernel
-    (ops.stft_1024_pcm), so a file's bytes travel to the GPU as they are (int16: half of float32's)."""
+    (ops.stft_1024_pcm), so a file's bytes travel to the GPU as they are (int16: half of float32's).
+    FLAC: decoded on the GPU and COPIED to host memory (not a memory map): int16 up to 16 bits, int32 above, samples
+    left-justified as WAV / AIFF store them (load_pcm_device keeps them on the device)."""
     data, sr = _read_frames(path, mmap=mmap)
     if data.dtype not in (np.int16, np.int32, np.uint8, np.float32):
         data = np.asarray(data, dtype=np.float32)  # (64-bit float files)
@@ -86,3 +93,84 @@ def save(path: str, wav: torch.Tensor, sample_rate: int) -> None:
     """(channels, samples) float tensor -> 32-bit float WAV (what torchaudio.save writes for float32 input)."""
     x = wav.detach().to("cpu", torch.float32).numpy()
     wavfile.write(path, int(sample_rate), np.ascontiguousarray(x.T))
+
+
+def _flac_region(path: str, device):
+    """(padded device buffer holding the audio region, its byte count, FlacInfo); the bytes are uploaded as they are"""
+    info = flac.read_header(path)  # a bad or missing file raises flac.FlacError (a ValueError naming the path) before any GPU check
+    from .. import ops
+    from .._lib import MusicGanHipError
+    if not torch.cuda.is_available():
+        raise MusicGanHipError(f"{path}: FLAC is decoded on the GPU and no ROCm GPU is available (there is no CPU decoder)")
+    n = info.audio_end - info.audio_offset
+    host = torch.zeros(ops.flac_padded_bytes(n), dtype=torch.uint8)
+    with open(path, "rb") as fh:
+        fh.seek(info.audio_offset)
+        got = fh.readinto(memoryview(host.numpy())[:n])
+    if got != n:
+        raise flac.FlacError(f"{path}: short read of the audio frames")
+    return host.to(device), n, info
+
+
+def load_pcm_device(path: str, device=None) -> torch.Tensor:
+    """The file's PCM frames (frames, channels) on the device, with the dtype and values load_pcm gives: a FLAC file is decoded
+    there (ops.flac_decode), any other format is read as stored and uploaded."""
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
+    if os.path.splitext(path)[1].lower() == ".flac":
+        buf, n, info = _flac_region(path, device)
+        from .. import ops
+        return ops.flac_decode(buf, info, nbytes=n, name=path)
+    data, _ = load_pcm(path, mmap=False)
+    if device is None:
+        from .._lib import MusicGanHipError
+        raise MusicGanHipError("load_pcm_device needs a ROCm GPU")
+    return torch.from_numpy(np.ascontiguousarray(data)).to(device)
+
+
+def info(path: str):
+    """(frames, channels, sample_rate, bits) from the file's headers alone, for every supported format.  A FLAC stream whose
+    STREAMINFO does not give the sample count is decoded to count it (on the GPU)."""
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".flac":
+        fi = flac.read_header(path)
+        frames = fi.total_samples
+        if frames == 0 and fi.audio_end > fi.audio_offset:
+            frames = load_pcm_device(path).shape[0]
+        return int(frames), fi.channels, fi.sample_rate, fi.bits
+    if ext in (".aif", ".aiff", ".aifc", ".au", ".snd"):
+        import aifc
+        import sunau
+        mod = sunau if ext in (".au", ".snd") else aifc
+        with mod.open(path, "rb") as f:
+            return int(f.getnframes()), int(f.getnchannels()), int(f.getframerate()), 8 * int(f.getsampwidth())
+    if ext not in (".wav", ".wave", ""):
+        _read_frames(path)  # raises the unsupported-format error
+    return _wav_info(path)
+
+
+def _wav_info(path: str):
+    """RIFF chunks: fmt (channels, rate, bits per sample) and the size of data"""
+    import struct
+    with open(path, "rb") as fh:
+        head = fh.read(12)
+        if len(head) < 12 or head[:4] not in (b"RIFF", b"RIFX") or head[8:12] != b"WAVE":
+            raise ValueError(f"{path}: not a RIFF WAVE file")
+        end = "<" if head[:4] == b"RIFF" else ">"
+        fmt = None
+        while True:
+            ck = fh.read(8)
+            if len(ck) < 8:
+                raise ValueError(f"{path}: no data chunk")
+            cid, size = ck[:4], struct.unpack(end + "I", ck[4:])[0]
+            if cid == b"fmt ":
+                body = fh.read(size + (size & 1))
+                _, ch, sr, _, align, bits = struct.unpack(end + "HHIIHH", body[:16])
+                fmt = (ch, sr, bits, align)
+            elif cid == b"data":
+                if fmt is None:
+                    raise ValueError(f"{path}: data chunk before fmt")
+                ch, sr, bits, align = fmt
+                return int(size // align), int(ch), int(sr), int(bits)
+            else:
+                fh.seek(size + (size & 1), 1)

@@ -173,11 +173,23 @@ class _Loader:
                 if self._stop:
                     return
                 t0 = time.perf_counter()
-                pcm, sr = audio.wavio.load_pcm(path)  # a memory map where the format allows: header parsed, no sample read yet
-                nbytes = pcm.size * pcm.dtype.itemsize
-                with th.cuda.stream(stream):
-                    dev = th.empty(nbytes, dtype=th.uint8, device=self.device)
-                offset = getattr(pcm, "offset", None)
+                fl = None
+                if os.path.splitext(path)[1].lower() == ".flac":
+                    # the compressed frames travel as they are (through the same staging buffers) and are decoded on this
+                    # worker's stream; the decoder's one status read-back is this file's only host synchronisation
+                    from . import ops
+                    fl = audio.wavio.flac.read_header(path)
+                    nbytes = fl.audio_end - fl.audio_offset
+                    pcm, sr, offset = None, fl.sample_rate, fl.audio_offset
+                    with th.cuda.stream(stream):
+                        dev = th.empty(ops.flac_padded_bytes(nbytes), dtype=th.uint8, device=self.device)
+                        dev[nbytes:].zero_()
+                else:
+                    pcm, sr = audio.wavio.load_pcm(path)  # a memory map where the format allows: header parsed, no sample read yet
+                    nbytes = pcm.size * pcm.dtype.itemsize
+                    with th.cuda.stream(stream):
+                        dev = th.empty(nbytes, dtype=th.uint8, device=self.device)
+                    offset = getattr(pcm, "offset", None)
                 fh = open(path, "rb") if offset is not None else None
                 flat = None if fh is not None else np.ascontiguousarray(pcm).reshape(-1).view(np.uint8)
                 try:
@@ -202,14 +214,21 @@ class _Loader:
                 finally:
                     if fh is not None:
                         fh.close()
-                with th.cuda.stream(stream):
-                    ready = th.cuda.Event()
-                    ready.record(stream)
-                shape, dt = (pcm.shape[0], pcm.shape[1]), tdt[pcm.dtype]
-                del pcm
+                if fl is not None:
+                    with th.cuda.stream(stream):
+                        item = ops.flac_decode(dev, fl, nbytes=nbytes, name=path)
+                        ready = th.cuda.Event()
+                        ready.record(stream)
+                else:
+                    with th.cuda.stream(stream):
+                        ready = th.cuda.Event()
+                        ready.record(stream)
+                    shape, dt = (pcm.shape[0], pcm.shape[1]), tdt[pcm.dtype]
+                    del pcm
+                    item = dev.view(dt).view(*shape)
                 with self._lock:
                     self.busy_s += time.perf_counter() - t0
-                out_q.put((path, dev.view(dt).view(*shape), sr, ready))
+                out_q.put((path, item, sr, ready))
         except BaseException as e:  # noqa: BLE001  (re-raised by the consumer)
             out_q.put(e)
 
@@ -272,8 +291,7 @@ def create_dataset(audio_path: str, dataset_output_dir: str, *, packed: bool = T
         th.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
         counts = []
         for p in w_p:
-            data, sr = audio.wavio.load_pcm(p)
-            frames = data.shape[0]
+            frames, _, sr, _ = audio.wavio.info(p)  # headers only: no audio is read
             if resample and sr != audio.SAMPLE_RATE:  # the samples come from the resampled signal: ceil(44100 L / sr) frames
                 from . import ops
                 frames = ops.resample_len(frames, sr, audio.SAMPLE_RATE)

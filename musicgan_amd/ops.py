@@ -1155,3 +1155,97 @@ def input_transform(x: torch.Tensor, side: int, eps: float = 1e-8) -> torch.Tens
     check(lib.mg_input_transform(_p(x), int(x.dtype == torch.float64), _p(out), _p(ws), ws.numel(), n, h, w, side, eps, _s()),
           "mg_input_transform")
     return out
+
+
+# ------------------------------------------------------------------ FLAC
+_FLAC_STATUS = 16
+_FLAC_F_CRC, _FLAC_F_END, _FLAC_F_HDR, _FLAC_F_SYNTAX, _FLAC_F_RANGE = 1, 2, 4, 8, 16
+
+
+def flac_padded_bytes(nbytes: int) -> int:
+    """size of the zero-filled device buffer that holds an audio region of `nbytes` bytes for flac_decode(..., nbytes=...)"""
+    return int(_lib.load().mg_flac_padded_bytes(int(nbytes)))
+
+
+def flac_decode(data: torch.Tensor, info, nbytes: Optional[int] = None, name: str = "<flac>") -> torch.Tensor:
+    """The audio region of a FLAC stream (uint8 on the device: the bytes from info.audio_offset to info.audio_end, see
+    audio/flac.py) -> (samples, channels) int16 (depths up to 16 bits) or int32, each sample left-justified in its container, as
+    wavio.load_pcm gives the same PCM stored in a WAV / AIFF file.  `nbytes`: `data` is already a buffer of flac_padded_bytes(nbytes)
+    bytes, zero past nbytes (else it is copied into one).  Reads the decode status back once (a host synchronisation of the current
+    stream; once more when STREAMINFO does not give the sample count, and per false frame-sync code met).  A corrupt or truncated
+    stream raises ValueError naming `name`, the frame and its byte offset in the file."""
+    from .audio.flac import FlacError
+    if not data.is_cuda or data.dtype != torch.uint8:
+        raise _lib.MusicGanHipError("flac_decode: uint8 GPU tensor expected (no CPU decoder)")
+    lib = _lib.load()
+    base = int(getattr(info, "audio_offset", 0))
+    if nbytes is None:
+        nbytes = data.numel()
+        buf = torch.zeros(flac_padded_bytes(nbytes), dtype=torch.uint8, device=data.device)
+        buf[:nbytes].copy_(data.reshape(-1))
+    else:
+        buf = data
+        if buf.numel() < flac_padded_bytes(nbytes) or not buf.is_contiguous():
+            raise _lib.MusicGanHipError("flac_decode: the buffer must hold flac_padded_bytes(nbytes) bytes")
+    ch, bits, rate = int(info.channels), int(info.bits), int(info.sample_rate)
+    dtype = torch.int16 if bits <= 16 else torch.int32
+    if nbytes == 0:
+        if info.total_samples:
+            raise FlacError(f"{name}: no audio frames (truncated file)")
+        return torch.empty((0, ch), dtype=dtype, device=data.device)
+    cap = nbytes // 64 + 256
+    dev = data.device
+    while True:
+        ws = torch.empty(lib.mg_flac_ws_bytes(nbytes, cap), dtype=torch.uint8, device=dev)
+        check(lib.mg_flac_scan(_p(buf), nbytes, _p(ws), ws.numel(), cap, _s()), "mg_flac_scan")
+        total = int(info.total_samples)
+        if total == 0:  # not in STREAMINFO: count the chained frames first
+            st = ws[:8 * _FLAC_STATUS].view(torch.int64).cpu()
+            if int(st[0]) > cap:
+                cap = int(st[0]) + 256
+                continue
+            total = int(st[2])
+        out = torch.empty((total, ch), dtype=dtype, device=dev)
+        planar = torch.empty((max(total, 1) * ch,), dtype=torch.int32, device=dev)
+        resumes = 0
+        while True:
+            check(lib.mg_flac_decode(_p(buf), nbytes, _p(ws), ws.numel(), cap, ch, bits, rate, _p(planar), _p(out), total, _s()),
+                  "mg_flac_decode")
+            st = [int(v) for v in ws[:8 * _FLAC_STATUS].view(torch.int64).cpu()]  # the one read-back per decode
+            ncand, nframes, chained, chain_err = st[0], st[1], st[2], st[3]
+            if ncand > cap:
+                break
+            first_bad = st[7]
+            if first_bad < nframes:
+                flags, start, dec_end, nxt = st[8], st[9], st[10], st[11]
+                where = f"frame {first_bad} at byte offset {base + start}"
+                if flags & _FLAC_F_HDR:
+                    raise FlacError(f"{name}: {where}: the frame header does not match STREAMINFO "
+                                    f"({rate} Hz, {bits} bits, {ch} channels)")
+                if flags & _FLAC_F_RANGE:
+                    raise FlacError(f"{name}: {where}: more samples than STREAMINFO's total of {total}")
+                if dec_end > nbytes:
+                    raise FlacError(f"{name}: {where}: truncated stream (the frame runs past the end of the file)")
+                if flags & (_FLAC_F_CRC | _FLAC_F_SYNTAX):
+                    raise FlacError(f"{name}: {where}: corrupt frame (CRC-16 mismatch or invalid subframe)")
+                # F_END alone: the chain took a false sync code inside this frame; resume it where the frame really ends
+                if first_bad < resumes:
+                    raise FlacError(f"{name}: {where}: the frame chain does not converge")
+                resumes = first_bad + 1
+                check(lib.mg_flac_rechain(_p(buf), nbytes, _p(ws), ws.numel(), cap, first_bad + 1, dec_end, _s()),
+                      "mg_flac_rechain")
+                if not info.total_samples:  # the count came from the false chain
+                    recount = int(ws[:8 * _FLAC_STATUS].view(torch.int64)[2].cpu())
+                    if recount != total:
+                        total = recount
+                        out = torch.empty((total, ch), dtype=dtype, device=dev)
+                        planar = torch.empty((max(total, 1) * ch,), dtype=torch.int32, device=dev)
+                continue
+            if chain_err:
+                raise FlacError(f"{name}: frame {st[4]} at byte offset {base + st[5]}: no valid frame header "
+                                f"(corrupt or truncated stream)")
+            if chained != total:
+                raise FlacError(f"{name}: frame {nframes} at byte offset {base + nbytes}: truncated stream "
+                                f"({chained} of {total} samples)")
+            return out
+        cap = ncand + 256
