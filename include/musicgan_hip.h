@@ -412,6 +412,27 @@ int mg_flac_rechain(const void* data, int64_t nbytes, void* ws, size_t ws_bytes,
 int mg_flac_decode(const void* data, int64_t nbytes, void* ws, size_t ws_bytes, int64_t cand_cap, int channels, int bits,
                    int sample_rate, int32_t* planar, void* out, int64_t out_frames, mg_stream_t stream);
 
+/* ------------------------------------------------------------------ FLAC encoding [torchaudio.save of a .flac path: functions.py:139,
+ * th_audio.save]
+ * 1-8 channels of `samples` samples at 16 or 24 bits, fixed blocking (4096), STREAMINFO-only streams.  The device writes the frames;
+ * the host prepends "fLaC" and STREAMINFO (its MD5 is hashed on the host from `pcm`).  Workspace (mg_flac_enc_ws_bytes) starts
+ * with int64 status[16]: [0] bytes of the frames, [1] smallest and [2] largest frame, [3] non-finite input values (nothing written
+ * is meaningful when non-zero), [4] the first one's index (channel * samples + sample), [5] non-zero when a frame's packed size
+ * disagrees with its analysis (an internal error).
+ * Host-only size queries: the workspace, and a bound on the whole file (header + STREAMINFO + frames, every subframe no larger
+ * than VERBATIM); the frames' output buffer needs mg_flac_enc_max_bytes - 42 bytes. */
+size_t mg_flac_enc_ws_bytes(int64_t samples, int channels);
+size_t mg_flac_enc_max_bytes(int64_t samples, int channels, int bits);
+/* x: (channels, samples) with rows row_stride elements apart, kind 0 float32 / 1 float64 / 2 int16 (bits 16 only).  Floats are
+ * quantised to clamp(rint(x 2^(bits-1)), -2^(bits-1), 2^(bits-1) - 1); writes planar int32 [channels][samples] and pcm, the
+ * interleaved little-endian samples of bits / 8 bytes each (STREAMINFO's MD5 input), and resets the status. */
+int mg_flac_enc_quantise(const void* x, int kind, int64_t row_stride, int channels, int64_t samples, int bits, int32_t* planar,
+                         void* pcm, void* ws, size_t ws_bytes, mg_stream_t stream);
+/* analyses and packs every frame of `planar` into out (4-byte aligned, ZERO FILLED, out_bytes >= mg_flac_enc_max_bytes - 42):
+ * the frames from byte 0, status [0] bytes long; each frame's CRC-8 and CRC-16 included. */
+int mg_flac_enc_frames(const int32_t* planar, int channels, int64_t samples, int bits, int sample_rate, void* ws, size_t ws_bytes,
+                       void* out, size_t out_bytes, mg_stream_t stream);
+
 /* ------------------------------------------------------------------ multi-layer chains on small maps
  * The <= 4x4 ends of both networks -- the generator's first blocks [generator.py:15-40,67-76: conv3x3 -> LeakyReLU -> PixelNorm
  * -> Upsample -> conv3x3 -> LeakyReLU -> PixelNorm] and the critic's last blocks + classifier [discriminator.py:14-34,60-70,

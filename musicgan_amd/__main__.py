@@ -22,7 +22,10 @@ _MODES = {
         (("-n", "--nb-vec"), dict(type=int, default=10)),
         (("-m", "--nb-music"), dict(type=int, default=5)),
         (("-o", "--output-dir"), dict(type=str, required=True)),
-    ], lambda a: (a.output_dir, a.rand_channels, a.gen_dict_state, a.nb_vec, a.nb_music)),
+        (("--format",), dict(dest="audio_format", choices=("wav", "flac"), default="wav",
+                             help="wav: 32-bit float (default); flac: 24-bit FLAC encoded on the GPU")),
+    ], lambda a: (a.output_dir, a.rand_channels, a.gen_dict_state, a.nb_vec, a.nb_music),
+        lambda a: {"audio_format": a.audio_format} if a.audio_format != "wav" else {}),
     "view_audio": ("view_audio", "view_audio", [
         (("--input-audio",), dict(type=str, required=True)),
         (("--image-idx",), dict(type=int, required=True)),

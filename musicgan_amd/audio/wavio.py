@@ -2,7 +2,8 @@
 load() mirrors torchaudio.load(normalize=True): float32 tensor (channels, samples) in [-1, 1] and the sample rate.
 Containers: RIFF WAV (scipy), AIFF / AIFF-C and Sun AU with linear PCM (Python's standard library) -- the uncompressed formats
 torchaudio's backends read without a codec -- and FLAC, whose frames are decoded on the GPU (ops.flac_decode; there is no CPU
-decoder, so reading FLAC without a GPU raises MusicGanHipError).  mp3 and ogg raise."""
+decoder, so reading FLAC without a GPU raises MusicGanHipError).  mp3 and ogg raise.
+save() writes 32-bit float WAV, or FLAC for a .flac path (encoded on the GPU, ops.flac_encode)."""
 from __future__ import annotations
 
 import os
@@ -89,8 +90,25 @@ def load_pcm(path: str, mmap: bool = True):
     return data, int(sr)
 
 
-def save(path: str, wav: torch.Tensor, sample_rate: int) -> None:
-    """(channels, samples) float tensor -> 32-bit float WAV (what torchaudio.save writes for float32 input)."""
+def save(path: str, wav: torch.Tensor, sample_rate: int, bits_per_sample=None) -> None:
+    """(channels, samples) float tensor -> 32-bit float WAV (what torchaudio.save writes for float32 input).  A path ending in
+    .flac (any case) is written as FLAC instead, as torchaudio picks the container from the extension: float32 / float64 / int16
+    samples, 16 or 24 bits (default 24 for floats), encoded on the GPU (ops.flac_encode).  `bits_per_sample` is for .flac only."""
+    if os.path.splitext(path)[1].lower() == ".flac":
+        from .. import ops
+        from .._lib import MusicGanHipError
+        try:
+            ops.flac_encode_args(wav, sample_rate, bits_per_sample)
+        except ValueError as e:
+            raise ValueError(f"{path}: {e}") from None
+        if not torch.cuda.is_available():
+            raise MusicGanHipError(f"{path}: FLAC is encoded on the GPU and no ROCm GPU is available (there is no CPU encoder)")
+        data = ops.flac_encode(wav.detach(), sample_rate, bits_per_sample, name=path)
+        with open(path, "wb") as fh:
+            fh.write(data.numpy().tobytes())
+        return
+    if bits_per_sample is not None:
+        raise ValueError(f"{path}: bits_per_sample is only accepted for .flac paths (WAV output is 32-bit float)")
     x = wav.detach().to("cpu", torch.float32).numpy()
     wavfile.write(path, int(sample_rate), np.ascontiguousarray(x.T))
 

@@ -1,6 +1,7 @@
 """Sampling driver with the reference's entry point `generate(output_dir, rand_channels, gen_dict_state, nb_vec, nb_music)`
 (/root/reference/music_gan/generate.py:12-65): a fully grown generator turns wide latents into (2, 512, 512 * nb_vec)
-magnitude / phase images, which the inverse codec + inverse STFT turn into `sound_{i}.wav` -- all of it on the GPU."""
+magnitude / phase images, which the inverse codec + inverse STFT turn into `sound_{i}.wav` (or `.flac` with audio_format="flac")
+-- all of it on the GPU."""
 import os
 
 import torch
@@ -18,7 +19,11 @@ def _load_generator(rand_channels: int, checkpoint: str, device: torch.device) -
     return net.to(device).eval()
 
 
-def generate(output_dir: str, rand_channels: int, gen_dict_state: str, nb_vec: int, nb_music: int) -> None:
+def generate(output_dir: str, rand_channels: int, gen_dict_state: str, nb_vec: int, nb_music: int,
+             audio_format: str = "wav") -> None:
+    """audio_format: "wav" (32-bit float, the reference's output) or "flac" (24-bit, encoded on the GPU)"""
+    if audio_format not in ("wav", "flac"):
+        raise ValueError(f"audio_format must be 'wav' or 'flac', got {audio_format!r}")
     if os.path.exists(output_dir) and not os.path.isdir(output_dir):
         raise NotADirectoryError(f"\"{output_dir}\" is not a directory")
     os.makedirs(output_dir, exist_ok=True)
@@ -34,4 +39,4 @@ def generate(output_dir: str, rand_channels: int, gen_dict_state: str, nb_vec: i
         # one item at a time: the level-7 activations of a 512 x (512 * nb_vec) image are ~1 GB each
         for idx, z in enumerate(latents.split(1, dim=0)):
             image = gen(z.contiguous(), 1.0)
-            audio.magn_phase_to_wav(image, os.path.join(output_dir, f"sound_{idx}.wav"), audio.SAMPLE_RATE)
+            audio.magn_phase_to_wav(image, os.path.join(output_dir, f"sound_{idx}.{audio_format}"), audio.SAMPLE_RATE)

@@ -1249,3 +1249,114 @@ def flac_decode(data: torch.Tensor, info, nbytes: Optional[int] = None, name: st
                                 f"({chained} of {total} samples)")
             return out
         cap = ncand + 256
+
+
+_FLAC_ENC_BLOCK = 4096
+_FLAC_ENC_STATUS = 16  # int64: [0] frame bytes, [1] min / [2] max frame size, [3] non-finite values, [4] the first one, [5] error
+
+
+def flac_encode_args(wav: torch.Tensor, sample_rate: int, bits_per_sample: Optional[int] = None):
+    """The checks of flac_encode that need no GPU: (channels, samples) view of `wav` and the bit depth, or ValueError."""
+    if not isinstance(wav, torch.Tensor):
+        raise ValueError(f"flac_encode: a tensor expected, got {type(wav).__name__}")
+    if wav.dtype not in (torch.float32, torch.float64, torch.int16):
+        raise ValueError(f"flac_encode: float32, float64 or int16 samples expected, got {wav.dtype}")
+    x = wav[None] if wav.dim() == 1 else wav
+    if x.dim() != 2:
+        raise ValueError(f"flac_encode: (channels, samples) or (samples,) expected, got shape {tuple(wav.shape)}")
+    if not 1 <= x.shape[0] <= 8:
+        raise ValueError(f"flac_encode: 1 to 8 channels, got {x.shape[0]}")
+    if isinstance(sample_rate, bool) or int(sample_rate) != sample_rate or not 1 <= int(sample_rate) < (1 << 20):
+        raise ValueError(f"flac_encode: sample rate {sample_rate} outside 1 .. 2^20 - 1 (the STREAMINFO field)")
+    if x.dtype == torch.int16:
+        if bits_per_sample not in (None, 16):
+            raise ValueError(f"flac_encode: int16 samples are written at 16 bits, not {bits_per_sample}")
+        bits = 16
+    else:
+        bits = 24 if bits_per_sample is None else bits_per_sample
+        if bits not in (16, 24):
+            raise ValueError(f"flac_encode: bits_per_sample must be 16 or 24, got {bits_per_sample}")
+    return x, int(bits)
+
+
+def flac_streaminfo(n: int, ch: int, bits: int, rate: int, min_frame: int, max_frame: int, md5: bytes) -> bytes:
+    """"fLaC" and the STREAMINFO block (the last metadata block) of a fixed-blocking stream of `n` samples"""
+    nframes = (n + _FLAC_ENC_BLOCK - 1) // _FLAC_ENC_BLOCK
+    block = n if nframes == 1 else _FLAC_ENC_BLOCK  # the minimum leaves out the last block unless it is the only one
+    v = 0
+    for value, width in ((block, 16), (block, 16), (min_frame, 24), (max_frame, 24), (rate, 20), (ch - 1, 3), (bits - 1, 5),
+                         (n, 36)):
+        v = (v << width) | value
+    body = v.to_bytes(18, "big") + md5
+    return b"fLaC" + bytes([0x80]) + len(body).to_bytes(3, "big") + body
+
+
+def flac_encode(wav: torch.Tensor, sample_rate: int, bits_per_sample: Optional[int] = None, name: str = "<flac>") -> torch.Tensor:
+    """(channels, samples) or (samples,) float32 / float64 / int16 samples -> a complete .flac file as a CPU uint8 tensor: what
+    torchaudio.save writes for a .flac path.  Floats are quantised to q = clamp(rint(x 2^(b-1)), -2^(b-1), 2^(b-1) - 1) (round half
+    to even, clipping silently), b = bits_per_sample, 16 or 24 (default 24); int16 is written at 16 bits as it is.  A CPU tensor is
+    moved to the GPU first.  Encoding runs on the device (csrc/flac_encode.hip); the host reads the status back once, downloads the
+    frame bytes, and computes STREAMINFO's MD5 of the quantised PCM on a thread while the device encodes.  A NaN or infinity raises
+    ValueError naming `name` and the first such sample."""
+    import hashlib
+    import threading
+    x, bits = flac_encode_args(wav, sample_rate, bits_per_sample)
+    ch, n = int(x.shape[0]), int(x.shape[1])
+    if not torch.cuda.is_available():
+        raise _lib.MusicGanHipError(f"{name}: FLAC is encoded on the GPU and no ROCm GPU is available (there is no CPU encoder)")
+    lib = _lib.load()
+    if n == 0:
+        return torch.frombuffer(bytearray(flac_streaminfo(0, ch, bits, int(sample_rate), 0, 0, hashlib.md5().digest())),
+                                dtype=torch.uint8)
+    dev = x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    x = x.to(dev)
+    if x.stride(1) != 1 or (ch > 1 and x.stride(0) < n):
+        x = x.contiguous()
+    stride = int(x.stride(0)) if ch > 1 else n
+    kind = {torch.float32: 0, torch.float64: 1, torch.int16: 2}[x.dtype]
+    nb = bits // 8
+    ws_bytes = int(lib.mg_flac_enc_ws_bytes(n, ch))
+    out_bytes = (int(lib.mg_flac_enc_max_bytes(n, ch, bits)) - 42 + 3) // 4 * 4
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    planar = torch.empty(ch * n, dtype=torch.int32, device=dev)
+    pcm = torch.empty(n * ch * nb, dtype=torch.uint8, device=dev)
+    out = torch.zeros(out_bytes, dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev)
+    check(lib.mg_flac_enc_quantise(_p(x), kind, stride, ch, n, bits, _p(planar), _p(pcm), _p(ws), ws_bytes, _s()),
+          "mg_flac_enc_quantise")
+    # the PCM travels to the host on a side stream and is hashed there while the frames are encoded
+    quantised = torch.cuda.Event()
+    quantised.record(stream)
+    side = torch.cuda.Stream(dev)
+    side.wait_event(quantised)
+    host_pcm = torch.empty(pcm.numel(), dtype=torch.uint8, pin_memory=True)
+    with torch.cuda.stream(side):
+        host_pcm.copy_(pcm, non_blocking=True)
+        copied = torch.cuda.Event()
+        copied.record(side)
+    pcm.record_stream(side)
+    digest = {}
+
+    def _md5():
+        copied.synchronize()
+        digest["md5"] = hashlib.md5(memoryview(host_pcm.numpy())).digest()
+
+    hasher = threading.Thread(target=_md5)
+    hasher.start()
+    try:
+        check(lib.mg_flac_enc_frames(_p(planar), ch, n, bits, int(sample_rate), _p(ws), ws_bytes, _p(out), out_bytes, _s()),
+              "mg_flac_enc_frames")
+        st = [int(v) for v in ws[:8 * _FLAC_ENC_STATUS].view(torch.int64).cpu()]  # the one status read
+    finally:
+        hasher.join()
+    total, min_frame, max_frame, nonfinite, first_bad, err = st[:6]
+    if nonfinite:
+        c, i = divmod(first_bad, n)
+        raise ValueError(f"{name}: {nonfinite} non-finite sample value(s) (NaN or infinity); the first is sample {i} of channel {c}")
+    if err or not 0 < total <= out_bytes:
+        raise _lib.MusicGanHipError(f"{name}: FLAC encoding failed its internal size check (status {st[:6]})")
+    head = flac_streaminfo(n, ch, bits, int(sample_rate), min_frame, max_frame, digest["md5"])
+    data = torch.empty(len(head) + total, dtype=torch.uint8)
+    data[:len(head)] = torch.frombuffer(bytearray(head), dtype=torch.uint8)
+    data[len(head):].copy_(out[:total])
+    return data
