@@ -412,6 +412,25 @@ int mg_flac_rechain(const void* data, int64_t nbytes, void* ws, size_t ws_bytes,
 int mg_flac_decode(const void* data, int64_t nbytes, void* ws, size_t ws_bytes, int64_t cand_cap, int channels, int bits,
                    int sample_rate, int32_t* planar, void* out, int64_t out_frames, mg_stream_t stream);
 
+/* ------------------------------------------------------------------ Ogg Vorbis decoding [torchaudio.load of a .ogg file:
+ * functions.py:43, th_audio.load]
+ * Vorbis I streams of 1-8 channels, blocksizes 64-8192, floor 1, residues 0 / 1 / 2.  The host walks the Ogg pages, checks the
+ * header pages, parses the headers and packs the setup (musicgan_amd/audio/vorbis.py pack_setup: `setup` int32 records, `fsetup`
+ * float32 VQ values, dB table, IMDCT twiddles and window slopes), all on the device.  `file`: the whole file on the device;
+ * `pages`: int64 [npages][4] (file offset, body offset, body bytes, payload offset); pages from `crc_from` on have their CRC-32
+ * checked; `packets`: int64 [npk][5] (payload offset, bytes, spectrum offset in floats, first returned frame before trimming,
+ * blockflag); `payload` (mg_vorbis_payload_bytes of the page bodies, 4-byte aligned) receives the page bodies back to back.
+ * out: (out_frames, channels) float32, frames trim_start .. trim_start + out_frames of the overlap-added stream.  `phases`: bit
+ * mask of the launches (1 pages, 2 packets, 4 spectrum, 8 imdct, 16 overlap, 32 status; 63 all).  Workspace (mg_vorbis_ws_bytes)
+ * starts with int64 status: [0] first page whose CRC does not check (-1: none), [1] first packet the device refused (-1: none),
+ * [2] its reason (1 not an audio packet, 2 mode out of range, 3 blockflag differs from the host's). */
+size_t mg_vorbis_payload_bytes(int64_t nbytes);
+size_t mg_vorbis_ws_bytes(int64_t packets, int64_t pages, int64_t spec_floats, int channels, int64_t cls_stride);
+int mg_vorbis_decode(const void* file, int64_t file_bytes, const int64_t* pages, int64_t npages, int64_t crc_from,
+                     const int32_t* setup, const float* fsetup, int channels, int blocksize0, int blocksize1, const int64_t* packets,
+                     int64_t npk, void* payload, int64_t payload_bytes, void* ws, size_t ws_bytes, int64_t spec_floats,
+                     int64_t cls_stride, float* out, int64_t out_frames, int64_t trim_start, int phases, mg_stream_t stream);
+
 /* ------------------------------------------------------------------ FLAC encoding [torchaudio.save of a .flac path: functions.py:139,
  * th_audio.save]
  * 1-8 channels of `samples` samples at 16 or 24 bits, fixed blocking (4096), STREAMINFO-only streams.  The device writes the frames;

@@ -162,6 +162,10 @@ SIGNATURES = {
     "mg_flac_scan": (c_int, [_P, c_int64, _P, c_size_t, c_int64, _P]),
     "mg_flac_rechain": (c_int, [_P, c_int64, _P, c_size_t, c_int64, c_int64, c_int64, _P]),
     "mg_flac_decode": (c_int, [_P, c_int64, _P, c_size_t, c_int64, c_int, c_int, c_int, _P, _P, c_int64, _P]),
+    "mg_vorbis_payload_bytes": (c_size_t, [c_int64]),
+    "mg_vorbis_ws_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int, c_int64]),
+    "mg_vorbis_decode": (c_int, [_P, c_int64, _P, c_int64, c_int64, _P, _P, c_int, c_int, c_int, _P, c_int64, _P, c_int64, _P,
+                                 c_size_t, c_int64, c_int64, _P, c_int64, c_int64, c_int, _P]),
     "mg_flac_enc_ws_bytes": (c_size_t, [c_int64, c_int]),
     "mg_flac_enc_max_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "mg_flac_enc_quantise": (c_int, [_P, c_int, c_int64, c_int, c_int64, c_int, _P, _P, _P, c_size_t, _P]),

@@ -107,6 +107,9 @@ def wav_to_stft(wav_p: str, nperseg: int = constant.N_FFT, stride: int = constan
     if os.path.splitext(wav_p)[1].lower() == ".flac":  # decoded on the device: the PCM never visits the host
         sr = wavio.flac.read_header(wav_p).sample_rate
         pcm = None
+    elif os.path.splitext(wav_p)[1].lower() in wavio.OGG_EXTS:  # Ogg Vorbis: likewise
+        sr = wavio.vorbis.read_header(wav_p).sample_rate
+        pcm = None
     else:
         pcm, sr = wavio.load_pcm(wav_p)
     assert resample or sr == constant.SAMPLE_RATE, \

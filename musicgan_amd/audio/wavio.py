@@ -1,8 +1,9 @@
 """Minimal audio file IO (the reference uses torchaudio.load/save, functions.py:43,139; torchaudio is not a dependency here).
 load() mirrors torchaudio.load(normalize=True): float32 tensor (channels, samples) in [-1, 1] and the sample rate.
 Containers: RIFF WAV (scipy), AIFF / AIFF-C and Sun AU with linear PCM (Python's standard library) -- the uncompressed formats
-torchaudio's backends read without a codec -- and FLAC, whose frames are decoded on the GPU (ops.flac_decode; there is no CPU
-decoder, so reading FLAC without a GPU raises MusicGanHipError).  mp3 and ogg raise.
+torchaudio's backends read without a codec -- FLAC, whose frames are decoded on the GPU (ops.flac_decode), and Ogg Vorbis
+(.ogg / .oga), whose packets are decoded on the GPU (ops.vorbis_decode) to float32, not clipped, as torchaudio returns it.  There
+is no CPU decoder for either: reading them without a GPU raises MusicGanHipError.  mp3, Opus, Ogg FLAC and the rest raise.
 save() writes 32-bit float WAV, or FLAC for a .flac path (encoded on the GPU, ops.flac_encode)."""
 from __future__ import annotations
 
@@ -12,7 +13,9 @@ import numpy as np
 import torch
 from scipy.io import wavfile
 
-from . import flac
+from . import flac, vorbis
+
+OGG_EXTS = (".ogg", ".oga")
 
 
 def _linear_pcm(raw: bytes, width: int, channels: int, what: str) -> np.ndarray:
@@ -53,9 +56,12 @@ def _read_frames(path: str, mmap: bool = False):
         return _linear_pcm(raw, width, ch, path), int(sr)
     if ext == ".flac":
         return load_pcm_device(path).cpu().numpy(), flac.read_header(path).sample_rate
+    if ext in OGG_EXTS:
+        pcm = load_pcm_device(path)  # parses the file first: a bad stream raises its ValueError before any GPU check
+        return pcm.cpu().numpy(), vorbis.read_header(path).sample_rate
     if ext not in (".wav", ".wave", ""):
-        raise ValueError(f"{path}: only WAV, AIFF, AU (linear PCM) and FLAC files can be read here; torchaudio's other "
-                         f"codec-backed formats (mp3, ogg, ...) need a decoder this build does not ship")
+        raise ValueError(f"{path}: only WAV, AIFF, AU (linear PCM), FLAC and Ogg Vorbis files can be read here; torchaudio's other "
+                         f"codec-backed formats (mp3, opus, ...) need a decoder this build does not ship")
     try:
         sr, data = wavfile.read(path, mmap=mmap)
     except ValueError:  # formats scipy cannot map (e.g. 24-bit)
@@ -83,7 +89,8 @@ def load_pcm(path: str, mmap: bool = True):
     format allows) and the sample rate -- what `load` normalises and transposes; the device path does both inside the STFT kernel
     (ops.stft_1024_pcm), so a file's bytes travel to the GPU as they are (int16: half of float32's).
     FLAC: decoded on the GPU and COPIED to host memory (not a memory map): int16 up to 16 bits, int32 above, samples
-    left-justified as WAV / AIFF store them (load_pcm_device keeps them on the device)."""
+    left-justified as WAV / AIFF store them (load_pcm_device keeps them on the device).  Ogg Vorbis: decoded on the GPU and copied
+    to host memory as float32."""
     data, sr = _read_frames(path, mmap=mmap)
     if data.dtype not in (np.int16, np.int32, np.uint8, np.float32):
         data = np.asarray(data, dtype=np.float32)  # (64-bit float files)
@@ -130,6 +137,21 @@ def _flac_region(path: str, device):
     return host.to(device), n, info
 
 
+def read_vorbis(path: str):
+    """(the file's bytes as a uint8 array, its parsed stream): every header checked on the host, before any GPU check; without a
+    GPU a valid stream raises MusicGanHipError"""
+    try:
+        with open(path, "rb") as fh:
+            raw = np.fromfile(fh, dtype=np.uint8)
+    except OSError as e:
+        raise vorbis.VorbisError(f"{path}: cannot read the ogg file ({e.strerror or e})") from e
+    vs = vorbis.parse(raw, path)
+    if not torch.cuda.is_available():
+        from .._lib import MusicGanHipError
+        raise MusicGanHipError(f"{path}: Ogg Vorbis is decoded on the GPU and no ROCm GPU is available (there is no CPU decoder)")
+    return raw, vs
+
+
 def load_pcm_device(path: str, device=None) -> torch.Tensor:
     """The file's PCM frames (frames, channels) on the device, with the dtype and values load_pcm gives: a FLAC file is decoded
     there (ops.flac_decode), any other format is read as stored and uploaded."""
@@ -139,6 +161,10 @@ def load_pcm_device(path: str, device=None) -> torch.Tensor:
         buf, n, info = _flac_region(path, device)
         from .. import ops
         return ops.flac_decode(buf, info, nbytes=n, name=path)
+    if os.path.splitext(path)[1].lower() in OGG_EXTS:
+        raw, vs = read_vorbis(path)
+        from .. import ops
+        return ops.vorbis_decode(torch.from_numpy(raw).to(device), vs, name=path)
     data, _ = load_pcm(path, mmap=False)
     if device is None:
         from .._lib import MusicGanHipError
@@ -150,6 +176,9 @@ def info(path: str):
     """(frames, channels, sample_rate, bits) from the file's headers alone, for every supported format.  A FLAC stream whose
     STREAMINFO does not give the sample count is decoded to count it (on the GPU)."""
     ext = os.path.splitext(path)[1].lower()
+    if ext in OGG_EXTS:
+        vi = vorbis.read_header(path)
+        return vi.frames, vi.channels, vi.sample_rate, 0  # no stored bit depth
     if ext == ".flac":
         fi = flac.read_header(path)
         frames = fi.total_samples

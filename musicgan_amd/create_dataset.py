@@ -173,8 +173,19 @@ class _Loader:
                 if self._stop:
                     return
                 t0 = time.perf_counter()
-                fl = None
-                if os.path.splitext(path)[1].lower() == ".flac":
+                fl = vs = None
+                ext = os.path.splitext(path)[1].lower()
+                if ext in audio.wavio.OGG_EXTS:
+                    # the whole file travels (through the same staging buffers) and is decoded on this worker's stream; the
+                    # pages are walked and the headers parsed here, on the host
+                    from . import ops
+                    raw = np.fromfile(path, dtype=np.uint8)
+                    vs = audio.wavio.vorbis.parse(raw, path)
+                    nbytes = raw.size
+                    pcm, sr, offset = raw, vs.setup.rate, None
+                    with th.cuda.stream(stream):
+                        dev = th.empty(nbytes, dtype=th.uint8, device=self.device)
+                elif ext == ".flac":
                     # the compressed frames travel as they are (through the same staging buffers) and are decoded on this
                     # worker's stream; the decoder's one status read-back is this file's only host synchronisation
                     from . import ops
@@ -214,7 +225,13 @@ class _Loader:
                 finally:
                     if fh is not None:
                         fh.close()
-                if fl is not None:
+                if vs is not None:
+                    with th.cuda.stream(stream):
+                        item = ops.vorbis_decode(dev, vs, name=path)
+                        ready = th.cuda.Event()
+                        ready.record(stream)
+                    del pcm
+                elif fl is not None:
                     with th.cuda.stream(stream):
                         item = ops.flac_decode(dev, fl, nbytes=nbytes, name=path)
                         ready = th.cuda.Event()

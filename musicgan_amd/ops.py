@@ -1251,6 +1251,86 @@ def flac_decode(data: torch.Tensor, info, nbytes: Optional[int] = None, name: st
         cap = ncand + 256
 
 
+# ------------------------------------------------------------------ Ogg Vorbis
+VORBIS_PHASES = (("pages", 1), ("packets", 2), ("spectrum", 4), ("imdct", 8), ("overlap", 16), ("status", 32))
+
+
+class VorbisJob:
+    """device buffers of one Ogg Vorbis decode (vorbis_prepare); vorbis_run launches its phases"""
+
+
+def vorbis_prepare(data: torch.Tensor, vs, name: str = "<ogg>") -> "VorbisJob":
+    """The whole file (uint8 on the device) and its parsed stream (audio/vorbis.py parse) -> the tables and buffers of the decode,
+    uploaded (no launch, no synchronisation)."""
+    import numpy as np
+    from .audio import vorbis
+    if not data.is_cuda or data.dtype != torch.uint8:
+        raise _lib.MusicGanHipError("vorbis_decode: uint8 GPU tensor expected (no CPU decoder)")
+    lib = _lib.load()
+    st = vs.setup
+    ch, (b0, b1) = st.channels, st.blocksize
+    dev = data.device
+    pages = vs.pages
+    pay_off = np.concatenate([[0], np.cumsum(pages.body_len)])
+    pg = np.stack([pages.offset, pages.body, pages.body_len, pay_off[:-1]], axis=1).astype(np.int64)
+    npk = len(vs.pkt_len)
+    nblk = np.where(vs.pkt_blockflag == 1, b1, b0).astype(np.int64)
+    spec_len = ch * (nblk // 2)
+    spec_off = np.cumsum(spec_len) - spec_len
+    ret = np.zeros(npk, dtype=np.int64)
+    ret[1:] = nblk[:-1] // 4 + nblk[1:] // 4
+    ret_start = np.cumsum(ret) - ret
+    pk = np.stack([vs.pkt_pay, vs.pkt_len, spec_off, ret_start, vs.pkt_blockflag], axis=1).astype(np.int64) if npk else \
+        np.zeros((1, 5), np.int64)
+    cls_stride = 0
+    for r in st.residues:  # classification bytes per packet: the most any residue needs at the long blocksize
+        size = b1 // 2 * (ch if r.type == 2 else 1)
+        parts = max(0, min(r.end, size) - min(r.begin, size)) // r.partition_size
+        cls_stride = max(cls_stride, (1 if r.type == 2 else ch) * (parts + st.books[r.classbook].dims))
+    cls_stride = (cls_stride + 15) // 16 * 16
+    ints, floats = vorbis.pack_setup(st)
+    j = VorbisJob()
+    j.name, j.vs, j.data, j.lib = name, vs, data, lib
+    j.npages, j.npk, j.ch, j.bs = len(pg), npk, ch, (b0, b1)
+    j.spec_floats = int(spec_len.sum())
+    j.cls_stride = cls_stride
+    j.pages = torch.from_numpy(pg).to(dev)
+    j.packets = torch.from_numpy(pk).to(dev)
+    j.setup = torch.from_numpy(ints).to(dev)
+    j.fsetup = torch.from_numpy(floats).to(dev)
+    j.payload = torch.zeros(lib.mg_vorbis_payload_bytes(int(pay_off[-1])), dtype=torch.uint8, device=dev)
+    j.ws = torch.empty(lib.mg_vorbis_ws_bytes(npk, len(pg), j.spec_floats, ch, cls_stride), dtype=torch.uint8, device=dev)
+    j.out = torch.empty((vs.frames, ch), dtype=torch.float32, device=dev)
+    return j
+
+
+def vorbis_run(j: "VorbisJob", phases: int = 63) -> None:
+    check(j.lib.mg_vorbis_decode(_p(j.data), j.data.numel(), _p(j.pages), j.npages, j.vs.header_pages, _p(j.setup), _p(j.fsetup),
+                                 j.ch, j.bs[0], j.bs[1], _p(j.packets), j.npk, _p(j.payload), j.payload.numel(), _p(j.ws),
+                                 j.ws.numel(), j.spec_floats, j.cls_stride, _p(j.out), j.out.shape[0], j.vs.trim_start, phases,
+                                 _s()), "mg_vorbis_decode")
+
+
+def vorbis_decode(data: torch.Tensor, vs, name: str = "<ogg>") -> torch.Tensor:
+    """A whole Ogg Vorbis file (uint8 on the device) and its parsed stream (audio/vorbis.py parse) -> (frames, channels) float32
+    on the device, not clipped (what torchaudio.load returns for Vorbis), trimmed by the granule positions.  Reads the status back
+    once (a host synchronisation of the current stream).  A page whose CRC-32 does not check raises ValueError naming `name`, the
+    page and its byte offset."""
+    from .audio.vorbis import VorbisError
+    j = vorbis_prepare(data, vs, name)
+    vorbis_run(j)
+    status = [int(v) for v in j.ws[:24].view(torch.int64).cpu()]  # the one read-back per decode
+    if status[0] >= 0:
+        k = status[0]
+        raise VorbisError(f"{name}: page {k} at byte offset {int(vs.pages.offset[k])}: CRC-32 mismatch (corrupt stream)")
+    if status[1] >= 0:
+        k = status[1]
+        pg = int(vs.pkt_page[k])
+        raise VorbisError(f"{name}: page {pg} at byte offset {int(vs.pages.offset[pg])}: audio packet {k} is corrupt "
+                          f"(reason {status[2]})")
+    return j.out
+
+
 _FLAC_ENC_BLOCK = 4096
 _FLAC_ENC_STATUS = 16  # int64: [0] frame bytes, [1] min / [2] max frame size, [3] non-finite values, [4] the first one, [5] error
 
