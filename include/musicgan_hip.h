@@ -452,6 +452,23 @@ int mg_flac_enc_quantise(const void* x, int kind, int64_t row_stride, int channe
 int mg_flac_enc_frames(const int32_t* planar, int channels, int64_t samples, int bits, int sample_rate, void* ws, size_t ws_bytes,
                        void* out, size_t out_bytes, mg_stream_t stream);
 
+/* ------------------------------------------------------------------ Ogg Vorbis encoding [torchaudio.save of a .ogg path:
+ * functions.py:139, th_audio.save]
+ * 1-8 channels of `samples` samples, long blocks (2048) only.  The host builds the setup (musicgan_amd/audio/vorbis_encode.py:
+ * `tables` int32 codewords / floor posts, `ftables` float32 window, DCT-IV twiddles and dB table, both on the device) and writes
+ * the header pages; the device writes the audio pages, numbered from `first_seq`, into out (out_bytes >= mg_vorbis_enc_max_bytes).
+ * x: (channels, samples) with rows row_stride elements apart, kind 0 float32 / 1 float64 / 2 int16.  s_db: the floor offset S(q).
+ * max_packet_bytes: the longest packet the setup's books can produce.  `phases`: bit mask of the launches (1 analysis, 2 count,
+ * 4 layout, 8 pack, 16 pages; 31 all).  Workspace (mg_vorbis_enc_ws_bytes) starts with int64 status[16]: [0] first non-finite
+ * input value (channel * samples + sample), [1] first coefficient beyond the books' range ((packet * channels + channel) * 1024
+ * + bin), -1 none; [2] packet bytes, [3] bytes of the audio pages, [4] pages, [5] / [6] internal errors (not -1 / 0: page table
+ * full, a packet longer than max_packet_bytes). */
+size_t mg_vorbis_enc_ws_bytes(int64_t samples, int channels, int64_t max_packet_bytes);
+size_t mg_vorbis_enc_max_bytes(int64_t samples, int channels, int64_t max_packet_bytes);
+int mg_vorbis_encode(const void* x, int kind, int64_t row_stride, int channels, int64_t samples, float s_db, const int32_t* tables,
+                     const float* ftables, int64_t max_packet_bytes, int first_seq, void* ws, size_t ws_bytes, void* out,
+                     size_t out_bytes, int phases, mg_stream_t stream);
+
 /* ------------------------------------------------------------------ multi-layer chains on small maps
  * The <= 4x4 ends of both networks -- the generator's first blocks [generator.py:15-40,67-76: conv3x3 -> LeakyReLU -> PixelNorm
  * -> Upsample -> conv3x3 -> LeakyReLU -> PixelNorm] and the critic's last blocks + classifier [discriminator.py:14-34,60-70,

@@ -22,8 +22,9 @@ _MODES = {
         (("-n", "--nb-vec"), dict(type=int, default=10)),
         (("-m", "--nb-music"), dict(type=int, default=5)),
         (("-o", "--output-dir"), dict(type=str, required=True)),
-        (("--format",), dict(dest="audio_format", choices=("wav", "flac"), default="wav",
-                             help="wav: 32-bit float (default); flac: 24-bit FLAC encoded on the GPU")),
+        (("--format",), dict(dest="audio_format", choices=("wav", "flac", "ogg"), default="wav",
+                             help="wav: 32-bit float (default); flac: 24-bit FLAC; ogg: Ogg Vorbis at quality 3 (both "
+                                  "encoded on the GPU)")),
     ], lambda a: (a.output_dir, a.rand_channels, a.gen_dict_state, a.nb_vec, a.nb_music),
         lambda a: {"audio_format": a.audio_format} if a.audio_format != "wav" else {}),
     "view_audio": ("view_audio", "view_audio", [

@@ -170,6 +170,10 @@ SIGNATURES = {
     "mg_flac_enc_max_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "mg_flac_enc_quantise": (c_int, [_P, c_int, c_int64, c_int, c_int64, c_int, _P, _P, _P, c_size_t, _P]),
     "mg_flac_enc_frames": (c_int, [_P, c_int, c_int64, c_int, c_int, _P, c_size_t, _P, c_size_t, _P]),
+    "mg_vorbis_enc_ws_bytes": (c_size_t, [c_int64, c_int, c_int64]),
+    "mg_vorbis_enc_max_bytes": (c_size_t, [c_int64, c_int, c_int64]),
+    "mg_vorbis_encode": (c_int, [_P, c_int, c_int64, c_int, c_int64, c_float, _P, _P, c_int64, c_int, _P, c_size_t, _P, c_size_t,
+                                 c_int, _P]),
     "mg_crc32_f64_ws_bytes": (c_size_t, [c_int, c_int64]),
     "mg_crc32_f64": (c_int, [_P, _P, _P, c_size_t, c_int, c_int64, _P]),
     "mg_pt_write_samples": (c_int, [_P, c_int, c_int64, ctypes.c_char_p, ctypes.c_char_p, c_int64, ctypes.c_char_p, c_int64, c_int, c_int64]),

@@ -4,7 +4,9 @@ Containers: RIFF WAV (scipy), AIFF / AIFF-C and Sun AU with linear PCM (Python's
 torchaudio's backends read without a codec -- FLAC, whose frames are decoded on the GPU (ops.flac_decode), and Ogg Vorbis
 (.ogg / .oga), whose packets are decoded on the GPU (ops.vorbis_decode) to float32, not clipped, as torchaudio returns it.  There
 is no CPU decoder for either: reading them without a GPU raises MusicGanHipError.  mp3, Opus, Ogg FLAC and the rest raise.
-save() writes 32-bit float WAV, or FLAC for a .flac path (encoded on the GPU, ops.flac_encode)."""
+save() writes 32-bit float WAV, FLAC for a .flac path (encoded on the GPU, ops.flac_encode) or Ogg Vorbis for a .ogg / .oga
+path (encoded on the GPU, ops.vorbis_encode; `compression` is the quality, -1 .. 10, default 3, as torchaudio names it).  There
+is no CPU encoder for either: writing them without a GPU raises MusicGanHipError and writes nothing."""
 from __future__ import annotations
 
 import os
@@ -97,11 +99,32 @@ def load_pcm(path: str, mmap: bool = True):
     return data, int(sr)
 
 
-def save(path: str, wav: torch.Tensor, sample_rate: int, bits_per_sample=None) -> None:
+def save(path: str, wav: torch.Tensor, sample_rate: int, bits_per_sample=None, compression=None) -> None:
     """(channels, samples) float tensor -> 32-bit float WAV (what torchaudio.save writes for float32 input).  A path ending in
     .flac (any case) is written as FLAC instead, as torchaudio picks the container from the extension: float32 / float64 / int16
-    samples, 16 or 24 bits (default 24 for floats), encoded on the GPU (ops.flac_encode).  `bits_per_sample` is for .flac only."""
-    if os.path.splitext(path)[1].lower() == ".flac":
+    samples, 16 or 24 bits (default 24 for floats), encoded on the GPU (ops.flac_encode).  `bits_per_sample` is for .flac only.
+    A path ending in .ogg or .oga is written as Ogg Vorbis (ops.vorbis_encode) at quality `compression` (-1 .. 10, default 3),
+    which is for those paths only."""
+    ext = os.path.splitext(path)[1].lower()
+    if compression is not None and ext not in OGG_EXTS:
+        raise ValueError(f"{path}: compression is only accepted for .ogg / .oga paths (the Vorbis quality)")
+    if ext in OGG_EXTS:
+        from .. import ops
+        from .._lib import MusicGanHipError
+        if bits_per_sample is not None:
+            raise ValueError(f"{path}: bits_per_sample is only accepted for .flac paths (Vorbis has no bit depth)")
+        try:
+            ops.vorbis_encode_args(wav, sample_rate, compression)
+        except ValueError as e:
+            raise ValueError(f"{path}: {e}") from None
+        if not torch.cuda.is_available():
+            raise MusicGanHipError(f"{path}: Ogg Vorbis is encoded on the GPU and no ROCm GPU is available (there is no CPU "
+                                   f"encoder)")
+        data = ops.vorbis_encode(wav.detach(), sample_rate, compression, name=path)
+        with open(path, "wb") as fh:
+            fh.write(data.numpy().tobytes())
+        return
+    if ext == ".flac":
         from .. import ops
         from .._lib import MusicGanHipError
         try:

@@ -1,7 +1,7 @@
 """Sampling driver with the reference's entry point `generate(output_dir, rand_channels, gen_dict_state, nb_vec, nb_music)`
 (/root/reference/music_gan/generate.py:12-65): a fully grown generator turns wide latents into (2, 512, 512 * nb_vec)
-magnitude / phase images, which the inverse codec + inverse STFT turn into `sound_{i}.wav` (or `.flac` with audio_format="flac")
--- all of it on the GPU."""
+magnitude / phase images, which the inverse codec + inverse STFT turn into `sound_{i}.wav` (`.flac` with audio_format="flac",
+`.ogg` with "ogg") -- all of it on the GPU."""
 import os
 
 import torch
@@ -21,9 +21,10 @@ def _load_generator(rand_channels: int, checkpoint: str, device: torch.device) -
 
 def generate(output_dir: str, rand_channels: int, gen_dict_state: str, nb_vec: int, nb_music: int,
              audio_format: str = "wav") -> None:
-    """audio_format: "wav" (32-bit float, the reference's output) or "flac" (24-bit, encoded on the GPU)"""
-    if audio_format not in ("wav", "flac"):
-        raise ValueError(f"audio_format must be 'wav' or 'flac', got {audio_format!r}")
+    """audio_format: "wav" (32-bit float, the reference's output), "flac" (24-bit) or "ogg" (Ogg Vorbis at the default quality),
+    the last two encoded on the GPU"""
+    if audio_format not in ("wav", "flac", "ogg"):
+        raise ValueError(f"audio_format must be 'ogg', 'wav' or 'flac', got {audio_format!r}")
     if os.path.exists(output_dir) and not os.path.isdir(output_dir):
         raise NotADirectoryError(f"\"{output_dir}\" is not a directory")
     os.makedirs(output_dir, exist_ok=True)

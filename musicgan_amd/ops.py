@@ -1440,3 +1440,99 @@ def flac_encode(wav: torch.Tensor, sample_rate: int, bits_per_sample: Optional[i
     data[:len(head)] = torch.frombuffer(bytearray(head), dtype=torch.uint8)
     data[len(head):].copy_(out[:total])
     return data
+
+
+# ------------------------------------------------------------------ Ogg Vorbis encoding
+VORBIS_ENC_PHASES = (("analysis", 1), ("count", 2), ("layout", 4), ("pack", 8), ("pages", 16))
+_VENC_STATUS = 16  # int64: [0] first non-finite value, [1] first coefficient out of range, [2] packet bytes, [3] page bytes,
+#                    [4] pages, [5] / [6] internal errors
+
+
+def vorbis_encode_args(wav: torch.Tensor, sample_rate: int, quality=3.0):
+    """The checks of vorbis_encode that need no GPU: (channels, samples) view of `wav` and the quality as a float, or ValueError."""
+    if not isinstance(wav, torch.Tensor):
+        raise ValueError(f"vorbis_encode: a tensor expected, got {type(wav).__name__}")
+    if wav.dtype not in (torch.float32, torch.float64, torch.int16):
+        raise ValueError(f"vorbis_encode: float32, float64 or int16 samples expected, got {wav.dtype}")
+    x = wav[None] if wav.dim() == 1 else wav
+    if x.dim() != 2:
+        raise ValueError(f"vorbis_encode: (channels, samples) or (samples,) expected, got shape {tuple(wav.shape)}")
+    if not 1 <= x.shape[0] <= 8:
+        raise ValueError(f"vorbis_encode: 1 to 8 channels, got {x.shape[0]}")
+    if x.shape[1] == 0:
+        raise ValueError("vorbis_encode: no samples (an Ogg Vorbis file of 0 frames is not written)")
+    if isinstance(sample_rate, bool) or int(sample_rate) != sample_rate or not 1 <= int(sample_rate) < (1 << 32):
+        raise ValueError(f"vorbis_encode: sample rate {sample_rate} outside 1 .. 2^32 - 1 (the identification header field)")
+    if quality is None:
+        quality = 3.0
+    if isinstance(quality, bool) or not isinstance(quality, (int, float)) or not -1.0 <= float(quality) <= 10.0:
+        raise ValueError(f"vorbis_encode: quality (compression) must be a number in [-1, 10], got {quality!r}")
+    return x, float(quality)
+
+
+class VorbisEncJob:
+    """device buffers of one Ogg Vorbis encode (vorbis_encode_prepare); vorbis_encode_run launches its phases"""
+
+
+_venc_tables = {}
+
+
+def vorbis_encode_prepare(wav: torch.Tensor, sample_rate: int, quality=3.0, name: str = "<ogg>") -> "VorbisEncJob":
+    """the input on the device, the setup's tables (uploaded once per channel count and device) and the buffers (no launch)"""
+    from .audio import vorbis_encode as VE
+    x, quality = vorbis_encode_args(wav, sample_rate, quality)
+    ch, n = int(x.shape[0]), int(x.shape[1])
+    if not torch.cuda.is_available():
+        raise _lib.MusicGanHipError(f"{name}: Ogg Vorbis is encoded on the GPU and no ROCm GPU is available (there is no CPU "
+                                    f"encoder)")
+    lib = _lib.load()
+    dev = x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    x = x.to(dev)
+    if x.stride(1) != 1 or (ch > 1 and x.stride(0) < n):
+        x = x.contiguous()
+    setup = VE.setup_for(ch)
+    key = (ch, str(dev))
+    if key not in _venc_tables:
+        _venc_tables[key] = (torch.from_numpy(setup.ints).to(dev), torch.from_numpy(setup.floats).to(dev))
+    j = VorbisEncJob()
+    j.name, j.lib, j.x, j.ch, j.n, j.rate = name, lib, x, ch, n, int(sample_rate)
+    j.kind = {torch.float32: 0, torch.float64: 1, torch.int16: 2}[x.dtype]
+    j.stride = int(x.stride(0)) if ch > 1 else n
+    j.s_db = VE.s_db(quality)
+    j.ti, j.tf = _venc_tables[key]
+    j.maxpk = setup.max_packet_bytes
+    j.head, j.nhead = VE.header_pages(ch, int(sample_rate))
+    j.ws = torch.empty(int(lib.mg_vorbis_enc_ws_bytes(n, ch, j.maxpk)), dtype=torch.uint8, device=dev)
+    j.out = torch.empty(int(lib.mg_vorbis_enc_max_bytes(n, ch, j.maxpk)), dtype=torch.uint8, device=dev)
+    return j
+
+
+def vorbis_encode_run(j: "VorbisEncJob", phases: int = 31) -> None:
+    check(j.lib.mg_vorbis_encode(_p(j.x), j.kind, j.stride, j.ch, j.n, j.s_db, _p(j.ti), _p(j.tf), j.maxpk, j.nhead, _p(j.ws),
+                                 j.ws.numel(), _p(j.out), j.out.numel(), phases, _s()), "mg_vorbis_encode")
+
+
+def vorbis_encode(wav: torch.Tensor, sample_rate: int, quality=3.0, name: str = "<ogg>") -> torch.Tensor:
+    """(channels, samples) or (samples,) float32 / float64 / int16 samples -> a complete Ogg Vorbis file as a CPU uint8 tensor:
+    what torchaudio.save writes for a .ogg path, `quality` being its `compression` (-1 .. 10, default 3).  Samples are not
+    clipped; int16 is read as v / 32768.  Encoding runs on the device (csrc/vorbis_encode.hip, setup in audio/vorbis_encode.py);
+    the host reads the status back once and downloads the pages.  A NaN or infinity raises ValueError naming `name` and the first
+    such sample; so does a value too large for the setup's books (|x| beyond about 30)."""
+    j = vorbis_encode_prepare(wav, sample_rate, quality, name)
+    vorbis_encode_run(j)
+    st = [int(v) for v in j.ws[:8 * _VENC_STATUS].view(torch.int64).cpu()]  # the one status read
+    if st[0] >= 0:
+        c, i = divmod(st[0], j.n)
+        raise ValueError(f"{name}: non-finite sample value (NaN or infinity); the first is sample {i} of channel {c}")
+    if st[1] >= 0:
+        blk, b = divmod(st[1], 1024)
+        p, c = divmod(blk, j.ch)
+        raise ValueError(f"{name}: channel {c} around sample {max(0, (p - 1) * 1024)} is too loud for the Vorbis setup's books "
+                         f"(coefficient {b} of block {p}; samples are not clipped, scale the input down)")
+    if st[5] not in (-1, 0) or st[6] != -1 or not 0 < st[3] <= j.out.numel():
+        raise _lib.MusicGanHipError(f"{name}: Ogg Vorbis encoding failed its internal checks (status {st[:7]})")
+    total = st[3]
+    data = torch.empty(len(j.head) + total, dtype=torch.uint8)
+    data[:len(j.head)] = torch.frombuffer(bytearray(j.head), dtype=torch.uint8)
+    data[len(j.head):].copy_(j.out[:total])
+    return data
