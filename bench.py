@@ -7,9 +7,13 @@ batch 64 per GPU, level 5 with the fade-in branch live (alpha = 0.5).
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (whole-step algorithmic FLOPs against the
-exact-fp32 MFMA peak, plus the dominant kernel timed live with HIP events) and, at N=1, `cpu_baseline` (the CPU oracle -- a
-plain-PyTorch port of the reference step as executed -- on a bounded sample).
+Prints ONE JSON line on rank 0: the headline figure and its `roofline` (whole-step FLOPs against the exact-fp32 MFMA peak:
+static arithmetic, nothing timed beyond the steps).  A plain run does only that: set-up, warm-up, the timed steps, the
+`--dump-outputs` arrays and the line.  `--full` measures the rest in the same run, after the headline: the dominant kernel
+timed live with HIP events (`roofline.dominant_kernel`), the 5 : 1 cadence (`secondary`), the other levels, alpha = 1, the
+STFT / codec / create_dataset / train-loop records, the sharded STFT at N > 1 and, at N=1, `cpu_baseline` (the CPU oracle --
+a plain-PyTorch port of the reference step as executed -- on a bounded sample); --no-extra / --no-cadence / --no-cpu-baseline
+leave parts of it out.
 """
 from __future__ import annotations
 
@@ -146,12 +150,20 @@ def dominant_kernel_probe(device, batch: int, iters: int = 100):
     out = {"name": "wino3x3_strip<2,8,ACT_POOL_MOUT> Winograd F(2x2,3x3) conv 48->64@128x128 + lrelu + avgpool + tile mask, 3x batch", "ms": ms,
            "flop": flop, "tflops": flop / ms / 1e9, "executed_tflops": flop / 2.25 / ms / 1e9,
            "algorithmic_bytes": n * (4.0 * 48 * 128 * 128 + 4.0 * 64 * 64 * 64 + 1.0 * 64 * 64 * 64)}
-    # HBM bytes per launch from rocprofv3 PMC passes (FETCH_SIZE x2 on gfx950 + WRITE_SIZE), measured by tools/measure_traffic.sh
-    tpath = os.path.join(ROOT, "profiles", "traffic_dominant_kernel.json")
-    if os.path.exists(tpath):
-        with open(tpath) as f:
-            out["hbm_traffic"] = json.load(f)
+    traffic = dominant_traffic()
+    if traffic is not None:
+        out["hbm_traffic"] = traffic
     return out
+
+
+def dominant_traffic():
+    """HBM bytes per launch of the dominant kernel from rocprofv3 PMC passes (FETCH_SIZE x2 on gfx950 + WRITE_SIZE), measured by
+    tools/measure_traffic.sh and committed under profiles/."""
+    tpath = os.path.join(ROOT, "profiles", "traffic_dominant_kernel.json")
+    if not os.path.exists(tpath):
+        return None
+    with open(tpath) as f:
+        return json.load(f)
 
 
 def time_step(level: int, batch: int, rand_channels: int, device, steps: int, warmup: int, seed: int = 1234, alpha: float = 0.5):
@@ -603,12 +615,16 @@ def main():
     ap.add_argument("--rand-channels", type=int, default=32)
     ap.add_argument("--alpha", type=float, default=0.5,
                     help="fade-in coefficient of the timed step (SURVEY 8(d): 0.5 and 1.0; utils.py:62-68 holds 1.0 once a block has faded in)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the dominant kernel, the 5 : 1 cadence, the other levels and alpha = 1, the "
+                         "STFT / codec / create_dataset / train-loop records, the sharded STFT (N > 1) and the CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the other levels' records, the STFT / codec / create_dataset records and the train-loop record")
+                    help="with --full: skip the other levels' records, the STFT / codec / create_dataset records, the train-loop record "
+                         "and the sharded STFT")
     ap.add_argument("--cpu-batch", type=int, default=64)
     ap.add_argument("--no-cadence", action="store_true",
-                    help="skip the 5 critic : 1 generator `secondary` record (profiling runs: the trace then holds D+G steps only)")
+                    help="with --full: skip the 5 critic : 1 generator `secondary` record")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write what the last one computed (losses, weights, Adam moments) as DIR/<name>.npy")
     args = ap.parse_args()
@@ -701,7 +717,7 @@ def main():
     # secondary figure: the reference's own cadence, five critic updates per generator update (train.py:189);
     # images/s counts the real images consumed (one batch per critic update).  Single GPU only.
     cadence = None
-    if world == 1 and not args.no_cadence:
+    if world == 1 and args.full and not args.no_cadence:
         def cycle():
             for _ in range(5):
                 stepper.d_step(x_real, alpha)
@@ -724,7 +740,7 @@ def main():
     # the whole-job figure is all ranks' frames over the slowest rank's time.
     stft_sharded = None
     dist_on = torch.distributed.is_available() and torch.distributed.is_initialized()
-    if dist_on and (world > 1 or os.environ.get("MG_FORCE_DP") == "1") and not args.no_extra:  # (1 rank: rehearsal only)
+    if dist_on and (world > 1 or os.environ.get("MG_FORCE_DP") == "1") and args.full and not args.no_extra:  # (1 rank: rehearsal only)
         from musicgan_amd import audio, ops
         wav = torch.rand(44100 * 600, device=device, generator=torch.Generator(device=device).manual_seed(7 + rank)) - 0.5
         frames = 1 + wav.numel() // 256
@@ -756,7 +772,6 @@ def main():
     if rank == 0:
         fpi = flops_per_image(args.level, args.rand_channels)
         xfpi = executed_flops_per_image(args.level, args.rand_channels, args.batch)
-        dom = dominant_kernel_probe(device, args.batch)
         line = {
             "metric": f"spectrogram-images/sec G+D step, 2x{side}x{side} bs{args.batch}",
             "value": images_per_s, "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -769,20 +784,22 @@ def main():
                        "global_batch": world * args.batch, "parallelism": f"dp{world}"},
             "roofline": {**step_roofline(fpi, xfpi, images_per_s / world),
                          # HBM bytes of ONE launch of the dominant kernel (per launch, like `dominant_kernel`), and of the whole step
-                         "traffic": (dom.get("hbm_traffic") or {}).get("bytes_per_launch"),
+                         "traffic": (dominant_traffic() or {}).get("bytes_per_launch"),
                          "step_traffic": step_traffic(args.level, args.batch),
                          "traffic_basis": "NOT measured in this run: rocprofv3 PMC passes (FETCH_SIZE x 2 + WRITE_SIZE, separate passes) read "
                                           "from profiles/traffic_dominant_kernel.json (tools/measure_traffic.sh) and "
-                                          "profiles/traffic_step_l5.json (tools/measure_step_traffic.sh), re-measured in round 6",
-                         # dominant launch, timed live with HIP events on its stream: frac = executed FLOPs over the peak
-                         "dominant_kernel": {**dom, "frac": dom["executed_tflops"] / MFMA_F32_PEAK_TFLOPS,
-                                             "algorithmic_frac": dom["tflops"] / MFMA_F32_PEAK_TFLOPS}},
+                                          "profiles/traffic_step_l5.json (tools/measure_step_traffic.sh), re-measured in round 6"},
         }
+        if args.full:
+            # dominant launch, timed live with HIP events on its stream: frac = executed FLOPs over the peak
+            dom = dominant_kernel_probe(device, args.batch)
+            line["roofline"]["dominant_kernel"] = {**dom, "frac": dom["executed_tflops"] / MFMA_F32_PEAK_TFLOPS,
+                                                   "algorithmic_frac": dom["tflops"] / MFMA_F32_PEAK_TFLOPS}
         if cadence is not None:
             line["secondary"] = cadence
         if stft_sharded is not None:
             line["stft_sharded"] = stft_sharded
-        extra = world == 1 and not args.no_extra and args.level == 5
+        extra = world == 1 and args.full and not args.no_extra and args.level == 5
         if extra:
             # SURVEY 8(d)'s other single-GPU figures, timed in the same run: BASELINE.json configs[1] and configs[4].  Every GPU
             # measurement comes before the first CPU baseline: the oracle's OpenMP workers keep spinning for a while after their
@@ -801,7 +818,7 @@ def main():
             line["alpha_1"] = level_record(device, args.rand_channels, 5, 64, 50, 20, "the headline configuration at alpha = 1.0", alpha=1.0)
             line["stft"] = stft_record(device, cpu=False)
             line.update(create_dataset_and_train_records(device, args.rand_channels))
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             # bounded samples (~25 s in all): 1 warm-up + 1 timed step at level 5 (~9 s per step), 1 + 3 at levels 4 and 3 (< 1 s per
             # step; SURVEY 8(d): min of three, the median beside it)
             line["cpu_baseline"] = cpu_baseline(args.level, args.rand_channels, args.cpu_batch, iters=1 if args.level >= 5 else 3)

@@ -8,5 +8,5 @@ python tools/ab_winoups.py 2>&1 | grep -v amdgpu > gpurun_out/r06_ab_winoups.txt
 python tools/l67_bounds.py 7 6 3 40 > gpurun_out/r06_l67_bounds_l7.txt 2>&1
 python tools/l67_bounds.py 6 6 3 40 > gpurun_out/r06_l67_bounds_l6.txt 2>&1
 python tools/l67_bounds.py 5 64 3 15 > gpurun_out/r06_bounds_l5.txt 2>&1
-python bench.py > gpurun_out/r06_bench_line.json 2> gpurun_out/r06_bench_line.err
-tail -c 300 gpurun_out/r06_bench_line.json
+python bench.py --full > profiles/r06_bench_line.json   # (every record of the line; straight into profiles/)
+tail -c 300 profiles/r06_bench_line.json
