@@ -583,6 +583,28 @@ size_t mg_input_transform_ws_bytes(int N, int H, int W, int S);
 int mg_input_transform(const void* x, int x_is_f64, float* out, void* ws, size_t ws_bytes, int N, int H, int W, int S, float eps,
                        mg_stream_t stream);
 
+/* Sliced Wasserstein distance between patches of Laplacian-pyramid levels (Karras et al., ICLR 2018): the evaluation metric of
+ * musicgan_amd/metrics.py, which the reference does not have (definition: DESIGN.md).  All float32 unless said otherwise.
+ * pyr_down: x (NC,H,W) -> out (NC,H/2,W/2), the 5x5 binomial filter with mirrored borders sampled at even positions.
+ * pyr_lap:  out = x - up(coarse), coarse (NC,H/2,W/2); up = zero-stuffing then 4x the same filter.  H, W even and >= 4.
+ * gather:   level (N,C,H,W) + centres (N,P,2) int32 (row, column; clamped to the legal range) -> rows row0 .. row0 + N*P of the
+ *           (rows_total, C*patch*patch) descriptor buffer, and (sum, sum of squares) of every image and channel in float64 at
+ *           stats[(row0/P + n), c, 0..1]; row0 a multiple of P.
+ * stats_finish: the (images, C, 2) float64 pairs -> norm (C,3) = (mean, 1/std, std) over images*per_image values per channel.
+ * project:  out (D,M), out[d][m] = sum_k ((desc[m][k] - mean_c) * rstd_c) * dirs[d][k], dirs (D,K), K = C*patch*patch.
+ * sort_segments: ascending in-place sort of S contiguous segments of M keys; finite values and +-inf (NaN: unspecified order).
+ * distance: out[0] = mean |a[i] - b[i]| over n values, summed in float64 in an order that depends on n alone. */
+int mg_swd_pyr_down(const float* x, float* out, int NC, int H, int W, mg_stream_t stream);
+int mg_swd_pyr_lap(const float* x, const float* coarse, float* out, int NC, int H, int W, mg_stream_t stream);
+int mg_swd_gather(const float* level, const int32_t* centres, float* desc, double* stats, int N, int C, int H, int W, int P, int patch,
+                  int64_t row0, int64_t rows_total, mg_stream_t stream);
+int mg_swd_stats_finish(const double* stats, float* norm, int64_t images, int C, int64_t per_image, mg_stream_t stream);
+int mg_swd_project(const float* desc, const float* norm, const float* dirs, float* out, int64_t M, int C, int patch, int D,
+                   mg_stream_t stream);
+int mg_swd_sort_segments(float* x, int S, int64_t M, mg_stream_t stream);
+size_t mg_swd_distance_ws_bytes(int64_t n);
+int mg_swd_distance(const float* a, const float* b, int64_t n, float* out, void* ws, size_t ws_bytes, mg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 """`python -m musicgan_amd <mode> ...`: the reference's four sub-commands with its positional names and flags
-(/root/reference/music_gan/__main__.py:11-124), declared as data and dispatched lazily (importing `train` pulls in the GPU
-library, `view_audio` pulls in matplotlib)."""
+(/root/reference/music_gan/__main__.py:11-124) and `evaluate`, which the reference does not have, declared as data and dispatched
+lazily (importing `train` pulls in the GPU library, `view_audio` pulls in matplotlib)."""
 import argparse
 import importlib
 
@@ -31,6 +31,17 @@ _MODES = {
         (("--input-audio",), dict(type=str, required=True)),
         (("--image-idx",), dict(type=int, required=True)),
     ], lambda a: (a.input_audio, a.image_idx)),
+    "evaluate": ("evaluate", "evaluate", [
+        (("gen_dict_state",), dict(type=str)),
+        (("rand_channels",), dict(type=int)),
+        (("-i", "--input-dataset"), dict(dest="input_dataset", type=str, required=True)),
+        (("--level",), dict(type=int, default=7, help="growth level of the checkpoint (7: fully grown, 512 x 512)")),
+        (("-n", "--nb-images"), dict(dest="nb_images", type=int, default=8192, help="images per set (clipped to the dataset)")),
+        (("--batch-size",), dict(dest="batch_size", type=int, default=16)),
+        (("--seed",), dict(type=int, default=0)),
+        (("-o", "--output"), dict(type=str, default=None, help="also write the result as JSON to this file")),
+    ], lambda a: (a.gen_dict_state, a.rand_channels, a.input_dataset),
+        lambda a: dict(level=a.level, nb_images=a.nb_images, batch_size=a.batch_size, seed=a.seed, output=a.output)),
 }
 
 

@@ -183,6 +183,14 @@ SIGNATURES = {
     "mg_codec_fwd_strided": (c_int, [_P, _P, _P, _P, c_size_t, _P, c_size_t, c_int, c_int, _P]),
     "mg_codec_inv_ws_bytes": (c_size_t, [c_int, c_int]),
     "mg_codec_inv": (c_int, [_P, _P, _P, _P, c_size_t, c_int, c_int, _P]),
+    "mg_swd_pyr_down": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
+    "mg_swd_pyr_lap": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
+    "mg_swd_gather": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64, _P]),
+    "mg_swd_stats_finish": (c_int, [_P, _P, c_int64, c_int, c_int64, _P]),
+    "mg_swd_project": (c_int, [_P, _P, _P, _P, c_int64, c_int, c_int, c_int, _P]),
+    "mg_swd_sort_segments": (c_int, [_P, c_int, c_int64, _P]),
+    "mg_swd_distance_ws_bytes": (c_size_t, [c_int64]),
+    "mg_swd_distance": (c_int, [_P, _P, c_int64, _P, _P, c_size_t, _P]),
 }
 
 _lib = None

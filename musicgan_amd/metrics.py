@@ -1,0 +1,214 @@
+"""Evaluation metric: the sliced Wasserstein distance (SWD) between local patches of Laplacian-pyramid levels of two image sets
+(Karras et al., "Progressive Growing of GANs", ICLR 2018).  One number per pyramid level says how far the generated spectrograms
+are from the data at that scale; it needs no pretrained network and works on any channel count.  The definition is stated in
+DESIGN.md ("Evaluation: sliced Wasserstein distance"); every step runs in the HIP kernels of csrc/swd.hip.
+
+    swd = SWD(512, 512, images=8192)
+    for batch in real:  swd.feed_real(batch)      # float32 cuda (n, C, H, W), any split
+    for batch in fake:  swd.feed_fake(batch)
+    swd.result()                                   # {"512": .., "256": .., ..., "16": .., "avg": ..}, x 1000 as in the paper
+
+All random draws (patch centres, directions) come from one CPU generator when the object is built, so a result depends on the
+seed and the images alone.  The two sets get independent centres, so SWD(A, B) and SWD(B, A) differ by sampling noise;
+sliced_wasserstein() itself is exactly symmetric."""
+from __future__ import annotations
+
+from typing import Dict, List, Optional, Tuple
+
+import torch
+
+from . import ops
+
+
+def pyramid_sides(side_h: int, side_w: int, min_side: int = 16) -> List[Tuple[int, int]]:
+    """(height, width) of every level, finest first: halved while the short side stays >= min_side"""
+    if side_h < 1 or side_w < 1 or min_side < 1:
+        raise ValueError(f"positive sides expected, got {side_h} x {side_w}, min_side {min_side}")
+    if min(side_h, side_w) < min_side:
+        raise ValueError(f"a {side_h} x {side_w} image is smaller than the smallest pyramid level ({min_side})")
+    sides = [(side_h, side_w)]
+    while min(sides[-1]) // 2 >= min_side and sides[-1][0] % 2 == 0 and sides[-1][1] % 2 == 0:
+        sides.append((sides[-1][0] // 2, sides[-1][1] // 2))
+    return sides
+
+
+def _check_pyramid(h: int, w: int, levels: int) -> None:
+    if levels < 1:
+        raise ValueError(f"levels must be >= 1, got {levels}")
+    f = 1 << (levels - 1)
+    if h % f or w % f:
+        raise ValueError(f"a {levels}-level pyramid needs sides divisible by {f}, got {h} x {w}")
+    if levels > 1 and min(h, w) // f < 2:
+        raise ValueError(f"the coarsest of {levels} levels of a {h} x {w} image is smaller than 2")
+
+
+def laplacian_pyramid(x: torch.Tensor, levels: int) -> List[torch.Tensor]:
+    """Laplacian pyramid of a float32 cuda batch (N, C, H, W), finest level first; the last entry is the Gaussian residual."""
+    if x.dim() != 4:
+        raise ValueError(f"(N, C, H, W) expected, got {tuple(x.shape)}")
+    _check_pyramid(x.shape[2], x.shape[3], levels)
+    out, g = [], x
+    for _ in range(levels - 1):
+        nxt = ops.swd_pyr_down(g)
+        out.append(ops.swd_pyr_lap(g, nxt))
+        g = nxt
+    if levels == 1:
+        ops._chk_swd("laplacian_pyramid", x)
+    out.append(g)
+    return out
+
+
+def patch_descriptors(level: torch.Tensor, centres: torch.Tensor, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                      row: int = 0, patch: int = 7) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The (C, patch, patch) neighbourhoods of `level` (N, C, H, W) around `centres` (N, P, 2) int32 (row, column), flattened
+    channel-major.  Returns (desc, stats): desc (M, C patch^2) raw descriptors, stats (M / P, C, 2) float64 per-image sums and
+    sums of squares.  `out` = such a pair to append to: this batch fills rows row .. row + N P (row a multiple of P)."""
+    if level.dim() != 4 or centres.dim() != 3 or centres.shape[0] != level.shape[0] or centres.shape[2] != 2:
+        raise ValueError(f"level (N, C, H, W) and centres (N, P, 2) expected, got {tuple(level.shape)}, {tuple(centres.shape)}")
+    n, c, h, w = level.shape
+    p = centres.shape[1]
+    if patch < 1 or patch % 2 == 0 or patch > min(h, w):
+        raise ValueError(f"an odd patch size <= {min(h, w)} expected for a {h} x {w} level, got {patch}")
+    if row % p:
+        raise ValueError(f"row offset {row} is not a multiple of the {p} patches per image")
+    if out is None:
+        if row:
+            raise ValueError("a row offset needs the buffers to append to")
+        ops._chk_swd("patch_descriptors", level)
+        out = (torch.empty((n * p, c * patch * patch), dtype=torch.float32, device=level.device),
+               torch.empty((n, c, 2), dtype=torch.float64, device=level.device))
+    desc, stats = out
+    if desc.dim() != 2 or desc.shape[1] != c * patch * patch or row + n * p > desc.shape[0] or \
+            tuple(stats.shape) != (desc.shape[0] // p, c, 2):
+        raise ValueError(f"rows {row} .. {row + n * p} of {c * patch * patch} numbers do not fit buffers of shape "
+                         f"{tuple(desc.shape)}, {tuple(stats.shape)}")
+    ops.swd_gather(level, centres, desc, stats, patch, row)
+    return desc, stats
+
+
+def channel_stats(stats: torch.Tensor, per_image: int) -> torch.Tensor:
+    """(images, C, 2) float64 sums -> (C, 3) float32 (mean, 1 / std, std), population statistics over images * per_image values
+    per channel, added in an order that does not depend on how the images arrived"""
+    return ops.swd_stats_finish(stats, per_image)
+
+
+def segmented_sort_(x: torch.Tensor) -> torch.Tensor:
+    """Sort every row of a contiguous float32 cuda (S, M) tensor ascending, in place.  Finite values and +-inf are totally
+    ordered (-0.0 and +0.0 in either order); NaN is outside the contract."""
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"a non-empty (S, M) tensor expected, got {tuple(x.shape)}")
+    return ops.swd_sort_segments_(x)
+
+
+def sliced_wasserstein(desc_a: torch.Tensor, stats_a: torch.Tensor, desc_b: torch.Tensor, stats_b: torch.Tensor,
+                       directions: torch.Tensor, *, patch: int = 7, out: Optional[torch.Tensor] = None,
+                       work: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One repeat of the distance: normalise both descriptor sets per channel, project them on the unit `directions` (D, K),
+    sort every direction's projections and return the mean |sorted A - sorted B| as a 0-dim cuda tensor (not yet x 1000).
+    `out`: a one-element float32 tensor to write to; `work`: a (2, D, M) float32 buffer to reuse."""
+    if desc_a.dim() != 2 or desc_a.shape != desc_b.shape:
+        raise ValueError(f"two descriptor sets of one shape expected, got {tuple(desc_a.shape)} and {tuple(desc_b.shape)}")
+    m, k = desc_a.shape
+    if directions.dim() != 2 or directions.shape[1] != k:
+        raise ValueError(f"directions (D, {k}) expected, got {tuple(directions.shape)}")
+    if stats_a.shape != stats_b.shape or stats_a.dim() != 3 or k != stats_a.shape[1] * patch * patch or m % stats_a.shape[0]:
+        raise ValueError(f"statistics (images, C, 2) with C * {patch}^2 = {k} expected, got {tuple(stats_a.shape)} and "
+                         f"{tuple(stats_b.shape)}")
+    d = directions.shape[0]
+    per_image = (m // stats_a.shape[0]) * patch * patch
+    ops._chk_swd("sliced_wasserstein", desc_a, desc_b, directions)
+    if work is None:
+        work = torch.empty((2, d, m), dtype=torch.float32, device=desc_a.device)
+    if out is None:
+        out = torch.empty((), dtype=torch.float32, device=desc_a.device)
+    ops.swd_project(desc_a, ops.swd_stats_finish(stats_a, per_image), directions, work[0], patch)
+    ops.swd_project(desc_b, ops.swd_stats_finish(stats_b, per_image), directions, work[1], patch)
+    ops.swd_sort_segments_(work.view(2 * d, m))
+    ops.swd_distance(work[0], work[1], out)
+    return out
+
+
+def draw(sides: List[Tuple[int, int]], channels: int, images: int, patches_per_image: int, patch: int, dir_repeats: int,
+         dirs_per_repeat: int, seed: int):
+    """The random draws of one evaluation, from one CPU generator seeded with `seed`: for each level from finest to coarsest the
+    (images, P, 2) centres of the first set (rows, then columns), those of the second set, then the (R, D, K) float32 standard
+    normal directions, each divided by its norm.  Returns [(centres_a, centres_b, directions)] per level (int32, int32, float32)."""
+    gen = torch.Generator().manual_seed(seed)
+    half, k = patch // 2, channels * patch * patch
+    out = []
+    for h, w in sides:
+        cen = []
+        for _ in range(2):
+            ys = torch.randint(half, h - half, (images, patches_per_image), generator=gen)
+            xs = torch.randint(half, w - half, (images, patches_per_image), generator=gen)
+            cen.append(torch.stack((ys, xs), dim=2).to(torch.int32))
+        dirs = torch.randn(dir_repeats, dirs_per_repeat, k, generator=gen, dtype=torch.float32)
+        out.append((cen[0], cen[1], dirs / dirs.norm(dim=2, keepdim=True)))
+    return out
+
+
+class SWD:
+    """Sliced Wasserstein distance between `images` real and `images` generated (channels, side_h, side_w) images.  Descriptors of
+    every level stay on the device (images * patches_per_image * channels * patch^2 floats per level and set), so each image is
+    seen once; feeding launches kernels only, result() does the projections, sorts and the one copy to the host."""
+
+    def __init__(self, side_h: int, side_w: int, channels: int = 2, images: int = 8192, patches_per_image: int = 128,
+                 patch: int = 7, dir_repeats: int = 4, dirs_per_repeat: int = 128, min_side: int = 16, seed: int = 0) -> None:
+        if channels < 1 or images < 1 or patches_per_image < 1 or dir_repeats < 1 or dirs_per_repeat < 1:
+            raise ValueError("channels, images, patches_per_image, dir_repeats and dirs_per_repeat must be positive")
+        if patch < 1 or patch % 2 == 0:
+            raise ValueError(f"an odd patch size expected, got {patch}")
+        if min_side < patch:
+            raise ValueError(f"the smallest level ({min_side}) is smaller than the patch ({patch})")
+        self.sides = pyramid_sides(side_h, side_w, min_side)
+        _check_pyramid(side_h, side_w, len(self.sides))
+        self.shape = (channels, side_h, side_w)
+        self.images, self.patches, self.patch = images, patches_per_image, patch
+        self.repeats, self.dirs = dir_repeats, dirs_per_repeat
+        self.draws = draw(self.sides, channels, images, patches_per_image, patch, dir_repeats, dirs_per_repeat, seed)
+        self._dev = None
+        self._count = [0, 0]
+
+    def _setup(self, device) -> None:
+        c, k, m = self.shape[0], self.shape[0] * self.patch ** 2, self.images * self.patches
+        self._dev = device
+        self._centres = [(a.to(device), b.to(device)) for a, b, _ in self.draws]
+        self._dirs = [d.to(device) for _, _, d in self.draws]
+        self._desc = [[torch.empty((m, k), dtype=torch.float32, device=device) for _ in range(2)] for _ in self.sides]
+        self._stats = [[torch.empty((self.images, c, 2), dtype=torch.float64, device=device) for _ in range(2)] for _ in self.sides]
+
+    def _feed(self, which: int, batch: torch.Tensor) -> None:
+        if batch.dim() != 4 or tuple(batch.shape[1:]) != self.shape:
+            raise ValueError(f"(n, {', '.join(map(str, self.shape))}) expected, got {tuple(batch.shape)}")
+        n, done = batch.shape[0], self._count[which]
+        if done + n > self.images:
+            raise ValueError(f"{done + n} images fed, the evaluation was sized for {self.images}")
+        ops._chk_swd("SWD.feed", batch)
+        if self._dev is None:
+            self._setup(batch.device)
+        for i, lvl in enumerate(laplacian_pyramid(batch, len(self.sides))):
+            patch_descriptors(lvl, self._centres[i][which][done:done + n], (self._desc[i][which], self._stats[i][which]),
+                              done * self.patches, self.patch)
+        self._count[which] = done + n
+
+    def feed_real(self, batch: torch.Tensor) -> None:
+        self._feed(0, batch)
+
+    def feed_fake(self, batch: torch.Tensor) -> None:
+        self._feed(1, batch)
+
+    def result(self) -> Dict[str, float]:
+        """{"<short side of the level>": SWD x 1000, ..., "avg": their plain average} as Python floats"""
+        if self._count != [self.images, self.images]:
+            raise ValueError(f"{self._count[0]} real and {self._count[1]} generated images fed, {self.images} of each expected")
+        m = self.images * self.patches
+        work = torch.empty((2, self.dirs, m), dtype=torch.float32, device=self._dev)
+        dist = torch.empty((len(self.sides), self.repeats), dtype=torch.float32, device=self._dev)
+        for i in range(len(self.sides)):
+            for r in range(self.repeats):
+                sliced_wasserstein(self._desc[i][0], self._stats[i][0], self._desc[i][1], self._stats[i][1], self._dirs[i][r],
+                                   patch=self.patch, out=dist[i, r], work=work)
+        host = dist.cpu().double()
+        out = {str(min(s)): float(host[i].mean() * 1000.0) for i, s in enumerate(self.sides)}
+        out["avg"] = float(sum(out.values()) / len(out))
+        return out

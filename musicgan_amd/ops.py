@@ -1536,3 +1536,81 @@ def vorbis_encode(wav: torch.Tensor, sample_rate: int, quality=3.0, name: str = 
     data[:len(j.head)] = torch.frombuffer(bytearray(j.head), dtype=torch.uint8)
     data[len(j.head):].copy_(j.out[:total])
     return data
+
+
+# ------------------------------------------------------------------ sliced Wasserstein distance (musicgan_amd/metrics.py)
+def _chk_swd(what: str, *ts, dtype=torch.float32):
+    for t in ts:
+        if not t.is_cuda:
+            raise _lib.MusicGanHipError(f"{what}: tensors on a ROCm GPU expected (no CPU fallback)")
+        if t.dtype != dtype or not t.is_contiguous():
+            raise _lib.MusicGanHipError(f"{what}: contiguous {dtype} expected, got {t.dtype} contiguous={t.is_contiguous()}")
+
+
+def swd_pyr_down(x: torch.Tensor) -> torch.Tensor:
+    """(N, C, H, W) -> (N, C, H/2, W/2): the 5 x 5 binomial filter with mirrored borders, sampled at even rows and columns"""
+    _chk_swd("swd_pyr_down", x)
+    n, c, h, w = x.shape
+    out = torch.empty((n, c, h // 2, w // 2), dtype=torch.float32, device=x.device)
+    check(_lib.load().mg_swd_pyr_down(_p(x), _p(out), n * c, h, w, _s()), "mg_swd_pyr_down")
+    return out
+
+
+def swd_pyr_lap(x: torch.Tensor, coarse: torch.Tensor) -> torch.Tensor:
+    """x - up(coarse) for x (N, C, H, W) and coarse (N, C, H/2, W/2)"""
+    _chk_swd("swd_pyr_lap", x, coarse)
+    n, c, h, w = x.shape
+    assert coarse.shape == (n, c, h // 2, w // 2)
+    out = torch.empty_like(x)
+    check(_lib.load().mg_swd_pyr_lap(_p(x), _p(coarse), _p(out), n * c, h, w, _s()), "mg_swd_pyr_lap")
+    return out
+
+
+def swd_gather(level: torch.Tensor, centres: torch.Tensor, desc: torch.Tensor, stats: torch.Tensor, patch: int, row: int) -> None:
+    """level (N, C, H, W), centres (N, P, 2) int32 -> rows row .. row + N P of desc (M, C patch^2) and the per-image float64
+    (sum, sum of squares) pairs stats[row / P + n, c]"""
+    _chk_swd("swd_gather", level, desc)
+    _chk_swd("swd_gather", centres, dtype=torch.int32)
+    _chk_swd("swd_gather", stats, dtype=torch.float64)
+    n, c, h, w = level.shape
+    p = centres.shape[1]
+    check(_lib.load().mg_swd_gather(_p(level), _p(centres), _p(desc), _p(stats), n, c, h, w, p, patch, row, desc.shape[0], _s()),
+          "mg_swd_gather")
+
+
+def swd_stats_finish(stats: torch.Tensor, per_image: int) -> torch.Tensor:
+    """(images, C, 2) float64 sums -> (C, 3) float32: mean, 1 / std, std (population) over images * per_image values per channel"""
+    _chk_swd("swd_stats_finish", stats, dtype=torch.float64)
+    images, c, _ = stats.shape
+    norm = torch.empty((c, 3), dtype=torch.float32, device=stats.device)
+    check(_lib.load().mg_swd_stats_finish(_p(stats), _p(norm), images, c, per_image, _s()), "mg_swd_stats_finish")
+    return norm
+
+
+def swd_project(desc: torch.Tensor, norm: torch.Tensor, dirs: torch.Tensor, out: torch.Tensor, patch: int) -> torch.Tensor:
+    """out (D, M) = dirs (D, K) times the normalised descriptors (M, K) transposed"""
+    _chk_swd("swd_project", desc, norm, dirs, out)
+    m, k = desc.shape
+    d = dirs.shape[0]
+    c = norm.shape[0]
+    assert dirs.shape == (d, k) and k == c * patch * patch and out.shape == (d, m) and norm.shape == (c, 3)
+    check(_lib.load().mg_swd_project(_p(desc), _p(norm), _p(dirs), _p(out), m, c, patch, d, _s()), "mg_swd_project")
+    return out
+
+
+def swd_sort_segments_(x: torch.Tensor) -> torch.Tensor:
+    """ascending in-place sort of every row of the contiguous (S, M) tensor x"""
+    _chk_swd("swd_sort_segments_", x)
+    s, m = x.shape
+    check(_lib.load().mg_swd_sort_segments(_p(x), s, m, _s()), "mg_swd_sort_segments")
+    return x
+
+
+def swd_distance(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """out (one float32) = mean |a - b|"""
+    _chk_swd("swd_distance", a, b, out)
+    assert a.shape == b.shape and out.numel() == 1
+    lib = _lib.load()
+    ws = workspace(lib.mg_swd_distance_ws_bytes(a.numel()), a.device)
+    check(lib.mg_swd_distance(_p(a), _p(b), a.numel(), _p(out), _p(ws), ws.numel(), _s()), "mg_swd_distance")
+    return out
