@@ -16,6 +16,12 @@ a test can commit the records it covers and compare.
 the call's result: a test may change the values a launch produced (never the addressing) to check that a comparison downstream
 notices.
 
+`Census.pre` (optional) is called as pre(name, record, bound) before the wrapped call, `bound` being the `inspect.BoundArguments`
+the record was made from (None where the arguments did not bind): the hook may replace entries of `bound.arguments`, and the call
+is made with what it left there.  `Census.unwind` (optional) is called as unwind(name, record) when the wrapped call raises, so a
+`pre` hook that keeps state per call can drop it.  tests/poison.py re-homes every tensor argument into a guarded allocation this way.
+`census(module)` wraps the public functions of another module in the same manner (the default is `musicgan_amd.ops`).
+
 Graph capture replays launches the census does not see: run under it with MG_GRAPHS=0 (or make at most two calls per update
 shape -- the stepper captures from the third)."""
 from __future__ import annotations
@@ -85,18 +91,24 @@ class Census:
     def __init__(self):
         self.calls = []   # every record, in call order
         self.post = None
+        self.pre = None
+        self.unwind = None
 
-    def record(self, name, fn, args, kwargs):
+    def bind(self, name, fn, args, kwargs):
+        """(record, BoundArguments or None) of one call"""
         try:
             bound = inspect.signature(fn).bind(*args, **kwargs)
         except TypeError:
-            return (name, (("args", tuple(describe(a) for a in args)),) + tuple((k, describe(v)) for k, v in sorted(kwargs.items())))
+            return (name, (("args", tuple(describe(a) for a in args)),) + tuple((k, describe(v)) for k, v in sorted(kwargs.items()))), None
         rec = []
         for k, v in bound.arguments.items():
             if k == "self":
                 continue
             rec.append((k, describe(v)))
-        return (name, tuple(rec))
+        return (name, tuple(rec)), bound
+
+    def record(self, name, fn, args, kwargs):
+        return self.bind(name, fn, args, kwargs)[0]
 
     @property
     def distinct(self):
@@ -114,26 +126,40 @@ def args_of(rec) -> dict:
     return dict(rec[1])
 
 
+def public_functions(module):
+    """The functions `census` wraps: the public ones defined in `module` itself."""
+    return [(name, fn) for name, fn in list(vars(module).items())
+            if not name.startswith("_") and inspect.isfunction(fn) and fn.__module__ == module.__name__]
+
+
 @contextlib.contextmanager
-def census():
+def census(module=None, classes=LAUNCHES_OF_CLASSES):
     import pytest
-    from musicgan_amd import ops
+    if module is None:
+        from musicgan_amd import ops as module
     c = Census()
 
     def wrap(name, fn):
         @functools.wraps(fn)
         def inner(*args, **kwargs):
-            rec = c.record(name, fn, args, kwargs)
+            rec, bound = c.bind(name, fn, args, kwargs)
             c.calls.append(rec)
-            out = fn(*args, **kwargs)
+            if c.pre is not None:
+                c.pre(name, rec, bound)
+            try:
+                out = fn(*bound.args, **bound.kwargs) if bound is not None else fn(*args, **kwargs)
+            except BaseException:
+                if c.unwind is not None:
+                    c.unwind(name, rec)
+                raise
             return c.post(name, rec, out) if c.post is not None else out
         return inner
 
     with pytest.MonkeyPatch.context() as mp:
-        for name, fn in list(vars(ops).items()):
-            if not name.startswith("_") and inspect.isfunction(fn) and fn.__module__ == ops.__name__:
-                mp.setattr(ops, name, wrap(name, fn))
-        for cls, meth in LAUNCHES_OF_CLASSES:
-            klass = getattr(ops, cls)
-            mp.setattr(klass, meth, wrap(f"{cls}.{meth}", getattr(klass, meth)))
+        for name, fn in public_functions(module):
+            mp.setattr(module, name, wrap(name, fn))
+        for cls, meth in classes:
+            klass = getattr(module, cls, None)
+            if klass is not None:
+                mp.setattr(klass, meth, wrap(f"{cls}.{meth}", getattr(klass, meth)))
         yield c
