@@ -605,6 +605,26 @@ int mg_swd_sort_segments(float* x, int S, int64_t M, mg_stream_t stream);
 size_t mg_swd_distance_ws_bytes(int64_t n);
 int mg_swd_distance(const float* a, const float* b, int64_t n, float* out, void* ws, size_t ws_bytes, mg_stream_t stream);
 
+/* Multi-scale structural similarity between pairs of images a, b (N,C,H,W) float32 in [-1, 1]: the sample-diversity metric of
+ * musicgan_amd/metrics.py, which the reference does not have (definition: DESIGN.md).  HOST queries (no GPU work): scales (0 when a
+ * side is below 11), window (the 11 float32 taps), tiles (workgroups per channel plane of an H x W level), scratch_bytes (the slots
+ * of every scale plus both images of every coarser scale).
+ * scale:  one scale of N pairs.  slots (N,C,tiles(H,W),2) float64 receives every tile's sums of cs and of ssim over its valid
+ *         pixels; a_next / b_next (N,C,H/2,W/2), both or none, receive the 2x2 means (H, W even), the next scale's input.
+ * finish: slots = the regions of the scales 0 .. S-1 of an H x W image one after the other, slot_doubles values in all -> values[row0
+ *         + n] = prod_s max(mean_s, 0)^w_s and, where terms != NULL, terms[(row0 + n), s] = mean_s (the CS mean of every scale but
+ *         the last, whose SSIM mean it is), in float64; added in index order.
+ * mean:   out[0] = the mean of n float64 values, added in an order that depends on n alone. */
+int mg_ssim_scales(int H, int W);
+int mg_ssim_window(float* taps);
+int64_t mg_ssim_tiles(int H, int W);
+size_t mg_ssim_scratch_bytes(int64_t N, int C, int H, int W);
+int mg_ssim_scale(const float* a, const float* b, float* a_next, float* b_next, double* slots, int64_t N, int C, int H, int W,
+                  mg_stream_t stream);
+int mg_ssim_finish(const double* slots, size_t slot_doubles, int64_t N, int C, int H, int W, double* values, double* terms,
+                   int64_t row0, int64_t rows_total, mg_stream_t stream);
+int mg_ssim_mean(const double* values, int64_t n, double* out, mg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,16 @@ lazily (importing `train` pulls in the GPU library, `view_audio` pulls in matplo
 import argparse
 import importlib
 
+_METRICS = ("swd", "msssim")
+
+
+def _metric_list(text: str):
+    names = tuple(t.strip() for t in text.split(","))
+    if any(n not in _METRICS for n in names) or len(set(names)) != len(names):
+        raise argparse.ArgumentTypeError(f"a comma-separated subset of {','.join(_METRICS)} expected, got {text!r}")
+    return names
+
+
 # mode -> (module, function, [(flags, kwargs)], lambda args: positional call arguments[, lambda args: keyword call arguments])
 _MODES = {
     "create_dataset": ("create_dataset", "create_dataset", [
@@ -40,8 +50,12 @@ _MODES = {
         (("--batch-size",), dict(dest="batch_size", type=int, default=16)),
         (("--seed",), dict(type=int, default=0)),
         (("-o", "--output"), dict(type=str, default=None, help="also write the result as JSON to this file")),
+        (("--metrics",), dict(type=_metric_list, default=None, metavar="swd,msssim",
+                              help="what to report (default: swd); msssim: MS-SSIM between random pairs of generated images "
+                                   "and of real ones -- a generated value well above the real one means mode collapse")),
     ], lambda a: (a.gen_dict_state, a.rand_channels, a.input_dataset),
-        lambda a: dict(level=a.level, nb_images=a.nb_images, batch_size=a.batch_size, seed=a.seed, output=a.output)),
+        lambda a: dict(level=a.level, nb_images=a.nb_images, batch_size=a.batch_size, seed=a.seed, output=a.output,
+                       **({"metrics": a.metrics} if a.metrics is not None else {}))),
 }
 
 

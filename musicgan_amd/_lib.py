@@ -191,6 +191,13 @@ SIGNATURES = {
     "mg_swd_sort_segments": (c_int, [_P, c_int, c_int64, _P]),
     "mg_swd_distance_ws_bytes": (c_size_t, [c_int64]),
     "mg_swd_distance": (c_int, [_P, _P, c_int64, _P, _P, c_size_t, _P]),
+    "mg_ssim_scales": (c_int, [c_int, c_int]),
+    "mg_ssim_window": (c_int, [POINTER(c_float)]),
+    "mg_ssim_tiles": (c_int64, [c_int, c_int]),
+    "mg_ssim_scratch_bytes": (c_size_t, [c_int64, c_int, c_int, c_int]),
+    "mg_ssim_scale": (c_int, [_P, _P, _P, _P, _P, c_int64, c_int, c_int, c_int, _P]),
+    "mg_ssim_finish": (c_int, [_P, c_size_t, c_int64, c_int, c_int, c_int, _P, _P, c_int64, c_int64, _P]),
+    "mg_ssim_mean": (c_int, [_P, c_int64, _P]),
 }
 
 _lib = None

@@ -1,4 +1,4 @@
-"""Evaluation metric: the sliced Wasserstein distance (SWD) between local patches of Laplacian-pyramid levels of two image sets
+"""Evaluation metrics.  (1) The sliced Wasserstein distance (SWD) between local patches of Laplacian-pyramid levels of two image sets
 (Karras et al., "Progressive Growing of GANs", ICLR 2018).  One number per pyramid level says how far the generated spectrograms
 are from the data at that scale; it needs no pretrained network and works on any channel count.  The definition is stated in
 DESIGN.md ("Evaluation: sliced Wasserstein distance"); every step runs in the HIP kernels of csrc/swd.hip.
@@ -10,14 +10,22 @@ DESIGN.md ("Evaluation: sliced Wasserstein distance"); every step runs in the HI
 
 All random draws (patch centres, directions) come from one CPU generator when the object is built, so a result depends on the
 seed and the images alone.  The two sets get independent centres, so SWD(A, B) and SWD(B, A) differ by sampling noise;
-sliced_wasserstein() itself is exactly symmetric."""
+sliced_wasserstein() itself is exactly symmetric.
+
+(2) MS-SSIM between pairs of images of ONE set (the other number Karras et al. report): how much the samples differ from each
+other.  A generator that repeats itself scores well on SWD and high here.  Definition: DESIGN.md ("Evaluation: MS-SSIM sample
+diversity"); kernels: csrc/ssim.hip through musicgan_amd/ssim_ops.py.
+
+    ms = MSSSIM(512, 512, pairs=4096)
+    for a, b in pairs_of_batches:  ms.feed(a, b)  # float32 cuda (n, C, H, W) each, values in [-1, 1], any split
+    ms.result()                                   # the mean over the pairs, 1 = identical images; ms.values: one per pair"""
 from __future__ import annotations
 
 from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from . import ops
+from . import ops, ssim_ops
 
 
 def pyramid_sides(side_h: int, side_w: int, min_side: int = 16) -> List[Tuple[int, int]]:
@@ -212,3 +220,84 @@ class SWD:
         out = {str(min(s)): float(host[i].mean() * 1000.0) for i, s in enumerate(self.sides)}
         out["avg"] = float(sum(out.values()) / len(out))
         return out
+
+
+# ------------------------------------------------------------------ MS-SSIM
+MSSSIM_WINDOW, MSSSIM_MAX_SCALES = 11, 5
+
+
+def ms_ssim_scales(h: int, w: int) -> int:
+    """The number of scales S of an h x w image: the largest S <= 5 with both sides divisible by 2^(S-1) and the short side of
+    the coarsest scale >= 11 (5 at 512 x 512, 4 at 128, 3 at 64, 2 at 32, 1 at 16: plain SSIM)."""
+    if min(h, w) < MSSSIM_WINDOW:
+        raise ValueError(f"a {h} x {w} image is smaller than the {MSSSIM_WINDOW} x {MSSSIM_WINDOW} window")
+    s = 1
+    while s < MSSSIM_MAX_SCALES and h % (1 << s) == 0 and w % (1 << s) == 0 and (min(h, w) >> s) >= MSSSIM_WINDOW:
+        s += 1
+    return s
+
+
+def _check_pairs(a: torch.Tensor, b: torch.Tensor) -> int:
+    if a.dim() != 4 or a.shape != b.shape or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError(f"two non-empty (n, C, H, W) batches of one shape expected, got {tuple(a.shape)} and {tuple(b.shape)}")
+    return ms_ssim_scales(a.shape[2], a.shape[3])
+
+
+def ms_ssim_terms(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """(n, S) float64: per pair the mean of cs over channels and valid pixels of the scales 0 .. S-2, then the mean of ssim of
+    the last scale -- the factors of ms_ssim before the clamp and the weights"""
+    scales = _check_pairs(a, b)
+    ssim_ops._chk_ssim("ms_ssim_terms", a, b)
+    values = torch.empty(a.shape[0], dtype=torch.float64, device=a.device)
+    terms = torch.empty((a.shape[0], scales), dtype=torch.float64, device=a.device)
+    ssim_ops.ms_ssim_into(a, b, values, terms)
+    return terms
+
+
+def ms_ssim(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """(n,) float64 cuda: MS-SSIM of every pair (a[i], b[i]) of two float32 cuda batches (n, C, H, W) with values in [-1, 1]; a
+    pair's value depends on its own pixels alone.  A negative mean at any scale makes the pair's value exactly 0."""
+    _check_pairs(a, b)
+    ssim_ops._chk_ssim("ms_ssim", a, b)
+    values = torch.empty(a.shape[0], dtype=torch.float64, device=a.device)
+    ssim_ops.ms_ssim_into(a, b, values)
+    return values
+
+
+class MSSSIM:
+    """Mean MS-SSIM over `pairs` pairs of (channels, side_h, side_w) images.  Feeding launches kernels only; result() takes the
+    mean on the device, in an order that depends on `pairs` alone, and makes the one copy to the host."""
+
+    def __init__(self, side_h: int, side_w: int, channels: int = 2, pairs: int = 4096) -> None:
+        if channels < 1 or pairs < 1:
+            raise ValueError("channels and pairs must be positive")
+        self.scales = ms_ssim_scales(side_h, side_w)
+        self.shape = (channels, side_h, side_w)
+        self.pairs = pairs
+        self._values = None
+        self._count = 0
+
+    def feed(self, a: torch.Tensor, b: torch.Tensor) -> None:
+        if a.dim() != 4 or a.shape != b.shape or tuple(a.shape[1:]) != self.shape or a.shape[0] < 1:
+            raise ValueError(f"two batches (n, {', '.join(map(str, self.shape))}) expected, got {tuple(a.shape)} and {tuple(b.shape)}")
+        n = a.shape[0]
+        if self._count + n > self.pairs:
+            raise ValueError(f"{self._count + n} pairs fed, the evaluation was sized for {self.pairs}")
+        ssim_ops._chk_ssim("MSSSIM.feed", a, b)
+        if self._values is None:
+            self._values = torch.empty(self.pairs, dtype=torch.float64, device=a.device)
+        ssim_ops.ms_ssim_into(a, b, self._values, None, self._count)
+        self._count += n
+
+    @property
+    def values(self) -> torch.Tensor:
+        """the per-pair values fed so far, float64 on the device"""
+        if self._values is None:
+            raise ValueError("no pair fed yet")
+        return self._values[:self._count]
+
+    def result(self) -> float:
+        if self._count != self.pairs:
+            raise ValueError(f"{self._count} pairs fed, {self.pairs} expected")
+        out = torch.empty(1, dtype=torch.float64, device=self._values.device)
+        return float(ssim_ops.ssim_mean(self._values, out).cpu()[0])
