@@ -343,6 +343,20 @@ typedef struct {
 } mg_adam_tensor_dev_t;
 int mg_adam_step_dev(const mg_adam_tensor_dev_t* desc, int n_tensors, float lr, float beta1, float beta2, float eps,
                      float grad_scale, mg_stream_t stream);
+/* mg_adam_step_dev with an exponential running average of the weights kept in the same pass: after the update of `param`,
+ * ema = ema + (param - ema) * ema_weight, ema_weight = 1 - decay in (0, 1].  param, exp_avg, exp_avg_sq and the step counters
+ * come out bit for bit as from mg_adam_step_dev; the average costs no launch of its own. */
+typedef struct {
+  float* param;
+  const float* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  int64_t numel;
+  int32_t* step;
+  float* ema;
+} mg_adam_tensor_dev_ema_t;
+int mg_adam_step_dev_ema(const mg_adam_tensor_dev_ema_t* desc, int n_tensors, float lr, float beta1, float beta2, float eps,
+                         float grad_scale, float ema_weight, mg_stream_t stream);
 
 /* ------------------------------------------------------------------ STFT [audio/functions.py:38-62]
  * wav: mono fp32 [L]; out_re/out_im: [512][T] (freq-major, Nyquist row dropped), T = 1 + L/256.  Periodic Hann(1024),

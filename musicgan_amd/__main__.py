@@ -25,7 +25,10 @@ _MODES = {
         (("run",), dict(type=str, metavar="RUN_NAME")),
         (("-o", "--out-path"), dict(dest="out_path", type=str, required=True)),
         (("-i", "--input-dataset"), dict(dest="input_dataset", type=str, required=True)),
-    ], lambda a: (a.run, a.input_dataset, a.out_path)),
+        (("--ema-decay",), dict(dest="ema_decay", type=float, default=0.0, metavar="D",
+                                help="also keep an exponential running average of the generator's weights, decay D per generator "
+                                     "update (one in five iterations; Karras et al. use 0.999), saved as gen_ema_K.pt; 0: off")),
+    ], lambda a: (a.run, a.input_dataset, a.out_path), lambda a: {"ema_decay": a.ema_decay} if a.ema_decay else {}),
     "generate": ("generate", "generate", [
         (("gen_dict_state",), dict(type=str)),
         (("rand_channels",), dict(type=int)),

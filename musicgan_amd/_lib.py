@@ -34,6 +34,10 @@ class AdamTensorDev(Structure):
                 ("numel", c_int64), ("step", c_void_p)]
 
 
+class AdamTensorDevEma(Structure):
+    _fields_ = AdamTensorDev._fields_ + [("ema", c_void_p)]
+
+
 class WgradJob(Structure):
     _fields_ = [("slab", c_void_p), ("slab_b", c_void_p), ("gw", c_void_p), ("gb", c_void_p), ("nsplit", c_int), ("Cout", c_int),
                 ("Cin", c_int), ("CoutP", c_int), ("CinP", c_int), ("accumulate", c_int)]
@@ -146,6 +150,7 @@ SIGNATURES = {
     "mg_smallnet_buffer_floats": (c_size_t, [c_int, c_int, c_int, c_int]),
     "mg_smallnet": (c_int, [_P, c_int, c_int, c_int, c_size_t, c_float, _P]),
     "mg_adam_step_dev": (c_int, [_P, c_int, c_float, c_float, c_float, c_float, c_float, _P]),
+    "mg_adam_step_dev_ema": (c_int, [_P, c_int, c_float, c_float, c_float, c_float, c_float, c_float, _P]),
     "mg_input_transform_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "mg_input_transform": (c_int, [_P, c_int, _P, _P, c_size_t, c_int, c_int, c_int, c_int, c_float, _P]),
     "mg_stft_1024": (c_int, [_P, _P, _P, c_int64, _P]),

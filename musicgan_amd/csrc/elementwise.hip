@@ -625,10 +625,18 @@ constexpr int ADAM_DEV_CHUNK = 56;
 struct AdamDevChunk {
   mg_adam_tensor_dev_t t[ADAM_DEV_CHUNK];
 };
+// With the running average of the weights: 56-byte records, 48 of them -- the argument struct of AdamDevChunk, byte for byte.
+constexpr int ADAM_DEV_EMA_CHUNK = 48;
+struct AdamDevEmaChunk {
+  mg_adam_tensor_dev_ema_t t[ADAM_DEV_EMA_CHUNK];
+};
+static_assert(sizeof(AdamDevEmaChunk) <= sizeof(AdamDevChunk), "the averaged step's argument struct outgrew the plain one");
 
-__global__ void __launch_bounds__(256) adam_dev_k(const AdamDevChunk desc, float lr, float beta1, float beta2, float eps,
-                                                  float grad_scale) {
-  const mg_adam_tensor_dev_t d = desc.t[blockIdx.y];
+// One record of either kind.  EMA: with the new parameter value still in a register, ema = ema + (p - ema) * ema_weight -- the
+// form of the first-moment update below, for which ema == p is an exact fixed point.
+template <bool EMA, class Rec>
+__device__ __forceinline__ void adam_dev_body(const Rec& d, float lr, float beta1, float beta2, float eps, float grad_scale,
+                                              float ema_weight) {
   const float t = (float)(*d.step + 1);  // count AFTER this update
   const float bc1 = 1.f - (beta1 > 0.f ? powf(beta1, t) : 0.f);
   const float bc2s = sqrtf(1.f - powf(beta2, t));
@@ -640,24 +648,31 @@ __global__ void __launch_bounds__(256) adam_dev_k(const AdamDevChunk desc, float
     const float denom = sqrtf(v) / bc2s + eps;
     p = p - step_size * (m / denom);
   };
-  // 16-byte path when the four arrays allow it (a tensor's slice of a flat gradient bucket may start at any multiple of 4 bytes)
+  float* ema = nullptr;
+  if constexpr (EMA) ema = d.ema;
+  // 16-byte path when the arrays allow it (a tensor's slice of a flat gradient bucket may start at any multiple of 4 bytes)
   const bool vec = ((d.numel & 3) == 0) &&
-                   (((uintptr_t)d.param | (uintptr_t)d.grad | (uintptr_t)d.exp_avg | (uintptr_t)d.exp_avg_sq) & 15) == 0;
+                   (((uintptr_t)d.param | (uintptr_t)d.grad | (uintptr_t)d.exp_avg | (uintptr_t)d.exp_avg_sq | (uintptr_t)ema) &
+                    15) == 0;
   if (vec) {
     const int64_t nq = d.numel >> 2;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nq; i += (int64_t)gridDim.x * blockDim.x) {
       const f32x4 g4 = reinterpret_cast<const f32x4*>(d.grad)[i];
       f32x4 p4 = reinterpret_cast<f32x4*>(d.param)[i], m4 = reinterpret_cast<f32x4*>(d.exp_avg)[i],
             v4 = reinterpret_cast<f32x4*>(d.exp_avg_sq)[i];
+      f32x4 e4;
+      if constexpr (EMA) e4 = reinterpret_cast<f32x4*>(ema)[i];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float p = p4[e], m = m4[e], v = v4[e];
         update(g4[e], p, m, v);
         p4[e] = p; m4[e] = m; v4[e] = v;
+        if constexpr (EMA) e4[e] = e4[e] + (p - e4[e]) * ema_weight;
       }
       reinterpret_cast<f32x4*>(d.param)[i] = p4;
       reinterpret_cast<f32x4*>(d.exp_avg)[i] = m4;
       reinterpret_cast<f32x4*>(d.exp_avg_sq)[i] = v4;
+      if constexpr (EMA) reinterpret_cast<f32x4*>(ema)[i] = e4;
     }
     return;
   }
@@ -667,10 +682,25 @@ __global__ void __launch_bounds__(256) adam_dev_k(const AdamDevChunk desc, float
     d.param[i] = p;
     d.exp_avg[i] = m;
     d.exp_avg_sq[i] = v;
+    if constexpr (EMA) {
+      const float a = ema[i];
+      ema[i] = a + (p - a) * ema_weight;
+    }
   }
 }
 
-__global__ void __launch_bounds__(64) adam_tick_k(const AdamDevChunk desc, int n) {
+__global__ void __launch_bounds__(256) adam_dev_k(const AdamDevChunk desc, float lr, float beta1, float beta2, float eps,
+                                                  float grad_scale) {
+  adam_dev_body<false>(desc.t[blockIdx.y], lr, beta1, beta2, eps, grad_scale, 0.f);
+}
+
+__global__ void __launch_bounds__(256) adam_dev_ema_k(const AdamDevEmaChunk desc, float lr, float beta1, float beta2, float eps,
+                                                      float grad_scale, float ema_weight) {
+  adam_dev_body<true>(desc.t[blockIdx.y], lr, beta1, beta2, eps, grad_scale, ema_weight);
+}
+
+template <class Chunk>
+__global__ void __launch_bounds__(64) adam_tick_k(const Chunk desc, int n) {
   if ((int)threadIdx.x < n) *desc.t[threadIdx.x].step += 1;
 }
 
@@ -840,8 +870,30 @@ extern "C" int mg_adam_step_dev(const mg_adam_tensor_dev_t* desc, int n_tensors,
     }
     hipLaunchKernelGGL(adam_dev_k, dim3(64, n), dim3(256), 0, (hipStream_t)stream, c, lr, beta1, beta2, eps, grad_scale);
     MG_CHECK_LAUNCH("mg_adam_step_dev");
-    hipLaunchKernelGGL(adam_tick_k, dim3(1), dim3(64), 0, (hipStream_t)stream, c, n);  // behind every reader of the counters
+    hipLaunchKernelGGL(adam_tick_k<AdamDevChunk>, dim3(1), dim3(64), 0, (hipStream_t)stream, c, n);  // behind every reader of the counters
     MG_CHECK_LAUNCH("mg_adam_step_dev(tick)");
+  }
+  return MG_OK;
+}
+
+extern "C" int mg_adam_step_dev_ema(const mg_adam_tensor_dev_ema_t* desc, int n_tensors, float lr, float beta1, float beta2,
+                                    float eps, float grad_scale, float ema_weight, mg_stream_t stream) {
+  MG_CHECK_ARG(desc && n_tensors > 0, "mg_adam_step_dev_ema: bad arguments");
+  MG_CHECK_ARG(ema_weight > 0.f && ema_weight <= 1.f, "mg_adam_step_dev_ema: ema_weight %g is outside (0, 1]", (double)ema_weight);
+  for (int first = 0; first < n_tensors; first += ADAM_DEV_EMA_CHUNK) {
+    const int n = n_tensors - first < ADAM_DEV_EMA_CHUNK ? n_tensors - first : ADAM_DEV_EMA_CHUNK;
+    AdamDevEmaChunk c;
+    for (int i = 0; i < n; ++i) {
+      c.t[i] = desc[first + i];
+      MG_CHECK_ARG(c.t[i].param && c.t[i].grad && c.t[i].exp_avg && c.t[i].exp_avg_sq && c.t[i].step && c.t[i].ema &&
+                       c.t[i].numel >= 0,
+                   "mg_adam_step_dev_ema: record %d has a null pointer", first + i);
+    }
+    hipLaunchKernelGGL(adam_dev_ema_k, dim3(64, n), dim3(256), 0, (hipStream_t)stream, c, lr, beta1, beta2, eps, grad_scale,
+                       ema_weight);
+    MG_CHECK_LAUNCH("mg_adam_step_dev_ema");
+    hipLaunchKernelGGL(adam_tick_k<AdamDevEmaChunk>, dim3(1), dim3(64), 0, (hipStream_t)stream, c, n);
+    MG_CHECK_LAUNCH("mg_adam_step_dev_ema(tick)");
   }
   return MG_OK;
 }

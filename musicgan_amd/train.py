@@ -108,12 +108,16 @@ def _latest_state(resume_from: str) -> str:
 def train(run_name: str, input_dataset_path: str, output_dir: str, *, nb_epoch: int = 1000, batch_size: int = 6,
           num_workers: int = 6, metric_every: int = 20, max_iters: int = 0, save_every: int = 1000,
           resume_from: str = None, fadein_lengths=None, train_lengths=None, rand_channels: int = 32,
-          use_packed_loader: bool = True, progress_hook=None) -> None:
+          use_packed_loader: bool = True, progress_hook=None, ema_decay: float = 0.0) -> None:
     """Reference signature plus keyword-only extensions (all defaulting to the reference's literals).  `resume_from`: a
     directory written by a previous run; its newest `train_state_k.pt` / `gen_k.pt` / `disc_k.pt` / `optim_*_k.pt` set is
     loaded (growth level, Grower counters, weights, Adam state, noise stream, position in the epoch, checkpoint numbering), after
     which the run continues exactly as the uninterrupted one would (tests/test_audio_gpu.py::test_resume_is_bit_identical).
-    `progress_hook(iter_idx)`: called at the end of every iteration (bench.py's `train_loop` record takes its time stamps there)."""
+    `progress_hook(iter_idx)`: called at the end of every iteration (bench.py's `train_loop` record takes its time stamps there).
+    `ema_decay` (0: off): the generator's optimizer keeps an exponential running average of the generator's weights with this
+    decay per generator update (Karras et al. 2018 use 0.999), written as `gen_ema_{k}.pt` next to `gen_{k}.pt`; the averages
+    travel in `optim_gen_{k}.pt`, so a resumed run continues them, and one resumed from a run without them starts them at the
+    resumed weights.  The critic has no average and training itself does not read the generator's."""
     assert isdir(input_dataset_path), f"\"{input_dataset_path}\" doesn't exist or is not a directory"
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -158,7 +162,7 @@ def train(run_name: str, input_dataset_path: str, output_dir: str, *, nb_epoch: 
     disc = networks.Discriminator(start_layer=7).to(device)
     from .dist import broadcast_parameters
     broadcast_parameters([gen, disc])
-    optim_gen = FusedAdam(gen.parameters(), lr=gen_lr, betas=betas)
+    optim_gen = FusedAdam(gen.parameters(), lr=gen_lr, betas=betas, ema_decay=ema_decay)
     optim_disc = FusedAdam(disc.parameters(), lr=disc_lr, betas=betas)
     noise = th.Generator(device=device)
     noise.manual_seed(base_seed + 7919 * (rank + 1))
@@ -268,7 +272,8 @@ def train(run_name: str, input_dataset_path: str, output_dir: str, *, nb_epoch: 
                     saver.request_save(gen, disc, optim_gen, optim_disc, alpha, train_state=lambda: {
                         "grower": grower.state_dict(), "level": gen.curr_layer, "iter_idx": iter_idx, "epoch": e,
                         "epoch_pos": pos, "base_seed": base_seed, "noise_rng": rng_states, "world": world,
-                        "saver": saver.state_dict_after_save()})
+                        "saver": saver.state_dict_after_save()},
+                        **({"gen_ema": lambda: optim_gen.averaged_state_dict(gen)} if ema_decay else {}))
                 else:
                     saver.tick()
             else:

@@ -97,7 +97,8 @@ class Grower:
 
 class Saver:
     """Every `save_every` calls of `request_save` writes `{disc,optim_disc,gen,optim_gen}_{k}.pt` (state dicts, the reference's
-    file names) into `output_dir`, plus six preview images of fresh samples when matplotlib is importable."""
+    file names) into `output_dir`, plus six preview images of fresh samples when matplotlib is importable -- and `gen_ema_{k}.pt`,
+    the generator's state dict with averaged weights, when the caller supplies one."""
 
     _PREVIEWS = 6
 
@@ -111,9 +112,12 @@ class Saver:
     def _path(self, stem: str, suffix: str = "pt") -> str:
         return os.path.join(self._dir, f"{stem}_{self._saves}.{suffix}")
 
-    def _write_checkpoint(self, gen, disc, optim_gen, optim_disc, train_state: Optional[Callable[[], dict]]) -> None:
+    def _write_checkpoint(self, gen, disc, optim_gen, optim_disc, train_state: Optional[Callable[[], dict]],
+                          gen_ema: Optional[Callable[[], dict]] = None) -> None:
         for stem, obj in (("disc", disc), ("optim_disc", optim_disc), ("gen", gen), ("optim_gen", optim_gen)):
             torch.save(obj.state_dict(), self._path(stem))
+        if gen_ema is not None:
+            torch.save(gen_ema(), self._path("gen_ema"))
         if train_state is not None:
             torch.save(train_state(), self._path("train_state"))
 
@@ -137,14 +141,16 @@ class Saver:
                     plt.close()
 
     def request_save(self, gen: Generator, disc: Discriminator, optim_gen, optim_disc, alpha: float,
-                     train_state: Optional[Callable[[], dict]] = None) -> bool:
+                     train_state: Optional[Callable[[], dict]] = None,
+                     gen_ema: Optional[Callable[[], dict]] = None) -> bool:
         """`train_state` (optional callable -> dict) is an extension over the reference: the growth level, the Grower counters
         and the iteration index are written next to the four reference files as `train_state_{k}.pt`, which is what
-        `train(..., resume_from=...)` needs (the reference saves weights only, utils.py:118-145)."""
+        `train(..., resume_from=...)` needs (the reference saves weights only, utils.py:118-145).  `gen_ema` (optional callable ->
+        dict, another extension): a state dict with the generator's keys, written as `gen_ema_{k}.pt`."""
         self._calls += 1
         if self._calls % self._every:
             return False
-        self._write_checkpoint(gen, disc, optim_gen, optim_disc, train_state)
+        self._write_checkpoint(gen, disc, optim_gen, optim_disc, train_state, gen_ema)
         self._write_previews(gen, alpha)
         self._saves += 1
         return True
