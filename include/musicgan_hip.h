@@ -639,6 +639,25 @@ int mg_ssim_finish(const double* slots, size_t slot_doubles, int64_t N, int C, i
                    int64_t row0, int64_t rows_total, mg_stream_t stream);
 int mg_ssim_mean(const double* values, int64_t n, double* out, mg_stream_t stream);
 
+/* ---- nearest neighbours in pixel space (csrc/nn.hip): squared L2 distances between rows of D float32 numbers, the kernels behind
+ * musicgan_amd/nn_ops.py and metrics.NearestNeighbours, which the reference does not have (definition: DESIGN.md).  HOST queries (no
+ * GPU work): chunk (the components one wave accumulates in float32, a compile-time constant), ws_bytes (the float32 partial sums of
+ * one sqdist launch: chunks x nq x nr).
+ * sqnorm: out[n] = sum_d x[n][d]^2 in float64, added in an order that depends on D alone.
+ * sqdist: dist[i][j] = max(0, qn[i] + rn[j] - 2 sum_d q[i][d] r[j][d]) in float64; q (nq,D), r (nr,D) row-major, qn / rn their
+ *         sqnorm.  The dot product is accumulated in float32 (exact-fp32 MFMA) inside chunks of D and in float64 across them, in
+ *         an order that depends on D alone: a pair's value does not depend on nq, nr or the rows around it.  Any nq, nr, D >= 1.
+ * merge:  best_d / best_i (nq,k): every query's k nearest so far, ascending by (distance, id); an empty slot is (DBL_MAX, -1).  The
+ *         nr candidates of dist (nq,nr) with the ids rid[nr] are inserted; a candidate whose id equals qid[i] >= 0 is skipped (qid
+ *         may be NULL: no query has an id).  1 <= k <= 16. */
+int mg_nn_chunk(void);
+size_t mg_nn_ws_bytes(int64_t nq, int64_t nr, int64_t D);
+int mg_nn_sqnorm(const float* x, int64_t n, int64_t D, double* out, mg_stream_t stream);
+int mg_nn_sqdist(const float* q, const float* r, const double* qn, const double* rn, int64_t nq, int64_t nr, int64_t D, double* dist,
+                 void* ws, size_t ws_bytes, mg_stream_t stream);
+int mg_nn_merge(const double* dist, const int64_t* qid, const int64_t* rid, double* best_d, int64_t* best_i, int64_t nq, int64_t nr,
+                int k, mg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

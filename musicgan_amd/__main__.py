@@ -4,7 +4,7 @@ lazily (importing `train` pulls in the GPU library, `view_audio` pulls in matplo
 import argparse
 import importlib
 
-_METRICS = ("swd", "msssim")
+_METRICS = ("swd", "msssim", "nn")
 
 
 def _metric_list(text: str):
@@ -53,9 +53,11 @@ _MODES = {
         (("--batch-size",), dict(dest="batch_size", type=int, default=16)),
         (("--seed",), dict(type=int, default=0)),
         (("-o", "--output"), dict(type=str, default=None, help="also write the result as JSON to this file")),
-        (("--metrics",), dict(type=_metric_list, default=None, metavar="swd,msssim",
+        (("--metrics",), dict(type=_metric_list, default=None, metavar="swd,msssim,nn",
                               help="what to report (default: swd); msssim: MS-SSIM between random pairs of generated images "
-                                   "and of real ones -- a generated value well above the real one means mode collapse")),
+                                   "and of real ones -- a generated value well above the real one means mode collapse; nn: RMS "
+                                   "distance to the nearest dataset image, of generated images and of real ones -- a generated "
+                                   "value well below the real one, or a smallest value near 0, means memorised samples")),
     ], lambda a: (a.gen_dict_state, a.rand_channels, a.input_dataset),
         lambda a: dict(level=a.level, nb_images=a.nb_images, batch_size=a.batch_size, seed=a.seed, output=a.output,
                        **({"metrics": a.metrics} if a.metrics is not None else {}))),

@@ -203,6 +203,11 @@ SIGNATURES = {
     "mg_ssim_scale": (c_int, [_P, _P, _P, _P, _P, c_int64, c_int, c_int, c_int, _P]),
     "mg_ssim_finish": (c_int, [_P, c_size_t, c_int64, c_int, c_int, c_int, _P, _P, c_int64, c_int64, _P]),
     "mg_ssim_mean": (c_int, [_P, c_int64, _P]),
+    "mg_nn_chunk": (c_int, []),
+    "mg_nn_ws_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "mg_nn_sqnorm": (c_int, [_P, c_int64, c_int64, _P, _P]),
+    "mg_nn_sqdist": (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_int64, _P, _P, c_size_t, _P]),
+    "mg_nn_merge": (c_int, [_P, _P, _P, _P, _P, c_int64, c_int64, c_int, _P]),
 }
 
 _lib = None

@@ -3,27 +3,41 @@ loads a generator saved by train() (`gen_{k}.pt`), draws as many samples from it
 sliced Wasserstein distance between the two sets per pyramid level (musicgan_amd/metrics.py) -- one number per scale, x 1000 as
 in the paper, lower is better.  With "msssim" among `metrics` it also reports MS-SSIM between random pairs of generated images
 next to the same number for pairs of real images: a generated value well above the real one means the generator repeats itself
-(mode collapse), which SWD does not show.  Single GPU."""
+(mode collapse), which SWD does not show.  With "nn" it reports how far generated images are from their nearest dataset image,
+next to the same number for real images against the rest of the dataset: a generator that replays its corpus scores perfectly on
+the other two and near zero here.  Single GPU."""
 import json
 from typing import Dict, Optional, Sequence
 
 import torch
 
 from . import audio, ops
-from .metrics import MSSSIM, SWD
+from .metrics import MSSSIM, SWD, NearestNeighbours
 from .networks import Generator
 
 _FINAL_LEVEL, _FULL_SIDE = 7, 512
 _LATENT_H, _LATENT_W = 2, 2
-METRICS = ("swd", "msssim")
+METRICS = ("swd", "msssim", "nn")
+# the nearest-neighbour check: queries per set, the side images are compared at (pixel L2 at 512 x 512 is dominated by sub-pixel
+# shifts and would cost 16 x more than the rest of the evaluation), neighbours kept per query
+_NN_QUERIES, _NN_SIDE, _NN_K = 256, 128, 1
 
 
 def evaluate(gen_dict_state: str, rand_channels: int, input_dataset: str, metrics: Sequence[str] = ("swd",), *,
              level: int = _FINAL_LEVEL, nb_images: int = 8192, batch_size: int = 16, seed: int = 0,
              output: Optional[str] = None) -> Dict[str, float]:
     """`level`: the growth level the checkpoint was saved at (7 = fully grown, 512 x 512); real samples are brought to that level's
-    side by the training loop's own input transform.  `metrics`: a subset of ("swd", "msssim").  Returns {"<side>": swd, ...,
-    "avg": swd, "msssim_real": .., "msssim_fake": ..} (the keys of the metrics asked for) and writes it as JSON to `output`."""
+    side by the training loop's own input transform.  `metrics`: a subset of ("swd", "msssim", "nn").  Returns {"<side>": swd, ...,
+    "avg": swd, "msssim_real": .., "msssim_fake": .., "nn_fake": .., "nn_real": .., "nn_fake_min": .., "nn_real_min": ..} (the keys
+    of the metrics asked for) and writes it as JSON to `output`.
+
+    "nn": the first min(nb_images, 256) generated images and as many real ones (random dataset entries, each barred from matching
+    itself) are compared with all `nb_images` real images at min(side, 128) pixels a side (larger images are reduced by 2 x 2
+    means).  Every number is a per-component RMS difference sqrt(d / D) to the nearest dataset image: `nn_fake` / `nn_real` the
+    mean over the queries, `nn_fake_min` / `nn_real_min` the smallest (one memorised sample does not move a mean).  `nn_fake`
+    well below `nn_real`, or `nn_fake_min` near 0, means memorisation.  Consecutive dataset entries are adjacent chunks of one
+    track, so a real image's nearest neighbour is often its own continuation and `nn_real` is small: that is the honest
+    calibration -- it is the distance at which the data resembles itself."""
     if not 0 <= level <= _FINAL_LEVEL:
         raise ValueError(f"level must be in 0 .. {_FINAL_LEVEL}, got {level}")
     if nb_images < 1 or batch_size < 1:
@@ -45,6 +59,8 @@ def evaluate(gen_dict_state: str, rand_channels: int, input_dataset: str, metric
         nb_images = len(dataset)
     if "msssim" in metrics and nb_images < 2:
         raise ValueError(f"MS-SSIM needs at least 2 images to pair, got {nb_images}")
+    if "nn" in metrics and nb_images < 2:
+        raise ValueError(f"nearest neighbours need at least 2 images (a real query may not match itself), got {nb_images}")
 
     print(f"Evaluate {nb_images} real and {nb_images} generated images of {side} x {side}...")
     rng = torch.Generator(device=device).manual_seed(seed)
@@ -62,10 +78,11 @@ def evaluate(gen_dict_state: str, rand_channels: int, input_dataset: str, metric
         result.update(swd.result())
         for name, value in result.items():
             print(f"SWD x 1e3 [{name:>3}] = {value:.4f}")
+    if "msssim" in metrics or "nn" in metrics:   # one seeded order of the dataset, shared by both
+        perm = torch.randperm(nb_images, generator=torch.Generator().manual_seed(seed)).tolist()
     if "msssim" in metrics:
         # random pairs, the same index pairs for both sets: consecutive dataset samples are adjacent chunks of one track, and
         # pairing neighbours would inflate the real number
-        perm = torch.randperm(nb_images, generator=torch.Generator().manual_seed(seed)).tolist()
         half = nb_images // 2
         first, second = perm[:half], perm[half:2 * half]
         ms_real, ms_fake = (MSSSIM(side, side, channels=2, pairs=half) for _ in range(2))
@@ -84,6 +101,36 @@ def evaluate(gen_dict_state: str, rand_channels: int, input_dataset: str, metric
         result["msssim_real"], result["msssim_fake"] = ms_real.result(), ms_fake.result()
         for name in ("msssim_real", "msssim_fake"):
             print(f"MS-SSIM [{name[7:]}] = {result[name]:.6f}")
+    if "nn" in metrics:
+        nq, cside = min(nb_images, _NN_QUERIES), min(side, _NN_SIDE)
+
+        def reduced(x):
+            while x.shape[-1] > cside:
+                x = ops.avgpool2_fwd(x)
+            return x
+
+        def real_at(idx):
+            return reduced(ops.input_transform(torch.stack([dataset[i] for i in idx]).to(device).contiguous(), side))
+
+        with torch.no_grad():
+            fake_q = torch.cat([reduced(gen(latents[lo:lo + batch_size].contiguous(), 1.0).contiguous())
+                                for lo in range(0, nq, batch_size)])[:nq].contiguous()
+            real_q = torch.cat([real_at(perm[lo:min(lo + batch_size, nq)]) for lo in range(0, nq, batch_size)])
+            nn_fake = NearestNeighbours(fake_q, k=_NN_K)
+            nn_real = NearestNeighbours(real_q, k=_NN_K, query_ids=perm[:nq])   # a real query does not match itself
+            for lo in range(0, nb_images, batch_size):
+                ids = list(range(lo, min(lo + batch_size, nb_images)))
+                real = real_at(ids)
+                nn_fake.feed(real, ids)
+                nn_real.feed(real, ids)
+        comps = fake_q[0].numel()
+        rms = {name: (nn.result()[0][:, 0].cpu() / comps).sqrt() for name, nn in (("fake", nn_fake), ("real", nn_real))}
+        for suffix, fn in (("", torch.mean), ("_min", torch.min)):
+            for name in ("fake", "real"):
+                result[f"nn_{name}{suffix}"] = float(fn(rms[name]))
+        for name in ("fake", "real"):
+            print(f"NN RMS [{name}] = {result['nn_' + name]:.6f} (smallest {result['nn_' + name + '_min']:.6f}) at {cside} x {cside}")
+        print("NN: fake well below real, or a smallest fake value near 0, means memorised training samples")
     if output is not None:
         with open(output, "w") as f:
             json.dump(result, f, indent=1)

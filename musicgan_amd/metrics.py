@@ -18,14 +18,24 @@ diversity"); kernels: csrc/ssim.hip through musicgan_amd/ssim_ops.py.
 
     ms = MSSSIM(512, 512, pairs=4096)
     for a, b in pairs_of_batches:  ms.feed(a, b)  # float32 cuda (n, C, H, W) each, values in [-1, 1], any split
-    ms.result()                                   # the mean over the pairs, 1 = identical images; ms.values: one per pair"""
+    ms.result()                                   # the mean over the pairs, 1 = identical images; ms.values: one per pair
+
+(3) Nearest training neighbours in pixel space (the third check of Karras et al.): did the generator copy its corpus?  Squared L2
+distances between flattened float32 images, exact to a derived bound at any size.  Definition and error analysis: DESIGN.md
+("Evaluation: nearest training neighbours"); kernels: csrc/nn.hip through musicgan_amd/nn_ops.py.
+
+    nn = NearestNeighbours(queries, k=1)          # float32 cuda (Q, ...), kept resident; query_ids: leave-one-out
+    for batch, ids in dataset:  nn.feed(batch, ids)   # (B, ...) of the same trailing shape, B distinct ids >= 0, any split / order
+    dist, idx = nn.result()                       # (Q, k) float64 squared distances ascending, (Q, k) int64 ids; both cuda
+    pairwise_sqdist(a, b)                         # the (Na, Nb) float64 distance matrix on its own"""
 from __future__ import annotations
 
+import operator
 from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from . import ops, ssim_ops
+from . import nn_ops, ops, ssim_ops
 
 
 def pyramid_sides(side_h: int, side_w: int, min_side: int = 16) -> List[Tuple[int, int]]:
@@ -301,3 +311,99 @@ class MSSSIM:
             raise ValueError(f"{self._count} pairs fed, {self.pairs} expected")
         out = torch.empty(1, dtype=torch.float64, device=self._values.device)
         return float(ssim_ops.ssim_mean(self._values, out).cpu()[0])
+
+
+# ------------------------------------------------------------------ nearest neighbours
+_NN_WS_BYTES = 256 << 20   # the partial sums of one distance launch stay below this: longer reference batches go in pieces
+
+
+def _rows(x: torch.Tensor, what: str) -> torch.Tensor:
+    """(N, ...) -> (N, D), a view; N >= 1 and D >= 1"""
+    if x.dim() < 2 or x.shape[0] < 1 or x[0].numel() < 1:
+        raise ValueError(f"{what}: a non-empty batch (N, ...) expected, got {tuple(x.shape)}")
+    nn_ops._chk_nn(what, x)
+    return x.view(x.shape[0], -1)
+
+
+def _sqdist(q: torch.Tensor, qn: torch.Tensor, r: torch.Tensor, out: torch.Tensor) -> None:
+    """out (nq, nr) = the distances of every (q[i], r[j]); r goes through in pieces of rows (a pair's value does not depend on
+    the piece it is in)"""
+    nq, nr, d = q.shape[0], r.shape[0], q.shape[1]
+    per_row = nn_ops.nn_ws_bytes(nq, 1, d)
+    step = max(16, _NN_WS_BYTES // per_row // 16 * 16)
+    if step >= nr:
+        nn_ops.nn_sqdist(q, r, qn, nn_ops.nn_sqnorm(r), out)
+        return
+    for lo in range(0, nr, step):
+        piece = r[lo:lo + step]
+        out[:, lo:lo + step] = nn_ops.nn_sqdist(q, piece, qn, nn_ops.nn_sqnorm(piece))
+
+
+def pairwise_sqdist(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """(Na, Nb) float64 cuda: the squared L2 distance between every a[i] and b[j] of two float32 cuda batches (Na, ...) and
+    (Nb, ...) with the same number of components per image; >= 0, and a pair's value depends on its two images alone."""
+    if a.dim() < 2 or b.dim() < 2 or a.shape[1:] != b.shape[1:] or a.numel() < 1 or b.numel() < 1:
+        raise ValueError(f"two non-empty batches of one trailing shape expected, got {tuple(a.shape)} and {tuple(b.shape)}")
+    a, b = _rows(a, "pairwise_sqdist"), _rows(b, "pairwise_sqdist")
+    out = torch.empty((a.shape[0], b.shape[0]), dtype=torch.float64, device=a.device)
+    _sqdist(a, nn_ops.nn_sqnorm(a), b, out)
+    return out
+
+
+def _id_list(ids, n: int, what: str) -> List[int]:
+    try:
+        ids = ids.tolist() if isinstance(ids, torch.Tensor) else [operator.index(i) for i in ids]
+    except TypeError:
+        raise ValueError(f"{what}: integers expected") from None
+    if len(ids) != n or any(not isinstance(i, int) for i in ids):
+        raise ValueError(f"{what}: {n} integers expected, got {len(ids)} entries")
+    return ids
+
+
+def _ids_to(ids: List[int], device) -> torch.Tensor:
+    """int64 on the device, through pinned memory: the copy does not make the host wait"""
+    return torch.tensor(ids, dtype=torch.int64).pin_memory().to(device, non_blocking=True)
+
+
+class NearestNeighbours:
+    """The k nearest of everything fed, by squared L2 distance, for each of Q resident query images.  `query_ids`: one integer
+    per query (-1: none); a fed image with a query's own id is not its neighbour (leave-one-out for queries taken from the fed
+    set).  The ids of all fed images are distinct and >= 0; ties in the distance go to the smaller id, so the result is the same
+    bit for bit for any split of the references into batches and any order of the batches.  Feeding launches kernels only."""
+
+    def __init__(self, queries: torch.Tensor, k: int = 1, query_ids=None) -> None:
+        if not isinstance(k, int) or not 1 <= k <= nn_ops.MAX_K:
+            raise ValueError(f"k in 1 .. {nn_ops.MAX_K} expected, got {k}")
+        self._q = _rows(queries, "NearestNeighbours")
+        self.k, self.shape = k, tuple(queries.shape[1:])
+        nq, dev = self._q.shape[0], queries.device
+        self._qid = None
+        if query_ids is not None:
+            ids = _id_list(query_ids, nq, "query_ids")
+            if any(i < -1 for i in ids):
+                raise ValueError("query_ids: ids >= 0, or -1 for a query without one, expected")
+            self._qid = _ids_to(ids, dev)
+        self._qn = nn_ops.nn_sqnorm(self._q)
+        self._best_d = torch.full((nq, k), nn_ops.EMPTY, dtype=torch.float64, device=dev)
+        self._best_i = torch.full((nq, k), -1, dtype=torch.int64, device=dev)
+        self._fed = 0
+
+    def feed(self, batch: torch.Tensor, ids) -> None:
+        if batch.dim() < 2 or tuple(batch.shape[1:]) != self.shape or batch.shape[0] < 1:
+            raise ValueError(f"a non-empty batch (B, {', '.join(map(str, self.shape))}) expected, got {tuple(batch.shape)}")
+        ids = _id_list(ids, batch.shape[0], "ids")
+        if len(set(ids)) != len(ids) or min(ids) < 0:
+            raise ValueError("ids: distinct integers >= 0 expected")
+        r = _rows(batch, "NearestNeighbours.feed")
+        dist = torch.empty((self._q.shape[0], r.shape[0]), dtype=torch.float64, device=r.device)
+        _sqdist(self._q, self._qn, r, dist)
+        nn_ops.nn_merge(dist, _ids_to(ids, r.device), self._best_d, self._best_i, self._qid)
+        self._fed += r.shape[0]
+
+    def result(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(dist, idx): (Q, k) float64 squared distances, ascending, and the (Q, k) int64 ids they belong to; copies, on the device"""
+        if self._fed < self.k:
+            raise ValueError(f"{self._fed} references fed, at least {self.k} expected")
+        if bool((self._best_i[:, -1] < 0).any()):   # a query whose own id was among fewer than k + 1 references
+            raise ValueError(f"{self._fed} references fed: some query has fewer than {self.k} neighbours that are not itself")
+        return self._best_d.clone(), self._best_i.clone()
