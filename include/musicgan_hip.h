@@ -569,6 +569,29 @@ size_t mg_codec_inv_ws_bytes(int N, int W);
 int mg_codec_inv(const float* magn_phase, const float* bark_scale, float* wav_out, void* ws, size_t ws_bytes, int N, int W,
                  mg_stream_t stream);
 
+/* ------------------------------------------------------------------ inverse STFT and Griffin-Lim phase refinement (csrc/griffinlim.hip)
+ * What torchaudio.functional.griffinlim (power = 1, rand_init = False) does for users of the reference, on spectra in
+ * mg_stft_1024's layout: 512 x TT interleaved complex64, frequency-major, TT = N * W >= 4 frames (definition: DESIGN.md).
+ * mg_codec_inv_spectrum: the front half of mg_codec_inv (the same four launches, the same bits).  magn_out [512][TT] receives the
+ *   target magnitude M = m / (max m - min m), z_c64 the spectrum mg_codec_inv inverts, or M + 0i if zero_phase != 0 (the phase image
+ *   is then not read).
+ * mg_istft_1024: the inverse of mg_stft_1024 -- Nyquist row zero, the imaginary part of DC ignored, periodic Hann(1024), hop 256,
+ *   times sqrt(sum w^2), overlap-add / window envelope, centre trimmed.  wav_out: [256 * (TT - 1)], 16-byte aligned.  One launch, no
+ *   workspace.
+ * mg_griffin_lim: with mu = momentum / (1 + momentum) and R_0 = 0, n_iter times: R_k = STFT(ISTFT(Z)), c = R_k - mu R_(k-1),
+ *   Z = M c / (|c| + 1e-16); then wav_out = ISTFT(Z).  z_c64 is read (the start) and rewritten (the last Z) if n_iter > 0;
+ *   convergence (may be NULL): [n_iter] float64, entry k = || |R_k| - M ||_2 / || M ||_2, float64 sums in a fixed order.  Three
+ *   launches per iteration and two at the end, all on `stream`, no allocation and no synchronisation: the call can be captured in
+ *   a graph (a single chain) once the library has run on the device.  All pointers 16-byte aligned; 0 <= momentum < 1.
+ *   ws_bytes: two spectra (R of the even and of the odd iterations) and the partial sums of every iteration. */
+size_t mg_codec_inv_spectrum_ws_bytes(int N, int W);
+int mg_codec_inv_spectrum(const float* magn_phase, const float* bark_scale, float* magn_out, float* z_c64, int zero_phase, void* ws,
+                          size_t ws_bytes, int N, int W, mg_stream_t stream);
+int mg_istft_1024(const float* z_c64, float* wav_out, int TT, mg_stream_t stream);
+size_t mg_griffin_lim_ws_bytes(int TT, int n_iter);
+int mg_griffin_lim(const float* magn, float* z_c64, float* wav_out, double* convergence, void* ws, size_t ws_bytes, int TT,
+                   int n_iter, float momentum, mg_stream_t stream);
+
 /* CRC-32 (zip / zlib) of the float64 widening of float32 samples: crc_out[i] = crc32 of the little-endian bytes of
  * x[i*floats_per_sample ...].astype(float64) -- the checksum the zip container of `th.save(sample.to(th.float64))`
  * [create_dataset.py:52-62] stores for its payload, which the reference's writer computes on one host core per sample.

@@ -38,8 +38,11 @@ _MODES = {
         (("--format",), dict(dest="audio_format", choices=("wav", "flac", "ogg"), default="wav",
                              help="wav: 32-bit float (default); flac: 24-bit FLAC; ogg: Ogg Vorbis at quality 3 (both "
                                   "encoded on the GPU)")),
+        (("--griffin-lim",), dict(dest="griffin_lim", type=int, default=0, metavar="N",
+                                  help="N rounds of Griffin-Lim phase refinement before the file is written (default 0: none)")),
     ], lambda a: (a.output_dir, a.rand_channels, a.gen_dict_state, a.nb_vec, a.nb_music),
-        lambda a: {"audio_format": a.audio_format} if a.audio_format != "wav" else {}),
+        lambda a: {**({"audio_format": a.audio_format} if a.audio_format != "wav" else {}),
+                   **({"griffin_lim": a.griffin_lim} if a.griffin_lim else {})}),
     "view_audio": ("view_audio", "view_audio", [
         (("--input-audio",), dict(type=str, required=True)),
         (("--image-idx",), dict(type=int, required=True)),

@@ -188,6 +188,11 @@ SIGNATURES = {
     "mg_codec_fwd_strided": (c_int, [_P, _P, _P, _P, c_size_t, _P, c_size_t, c_int, c_int, _P]),
     "mg_codec_inv_ws_bytes": (c_size_t, [c_int, c_int]),
     "mg_codec_inv": (c_int, [_P, _P, _P, _P, c_size_t, c_int, c_int, _P]),
+    "mg_codec_inv_spectrum_ws_bytes": (c_size_t, [c_int, c_int]),
+    "mg_codec_inv_spectrum": (c_int, [_P, _P, _P, _P, c_int, _P, c_size_t, c_int, c_int, _P]),
+    "mg_istft_1024": (c_int, [_P, _P, c_int, _P]),
+    "mg_griffin_lim_ws_bytes": (c_size_t, [c_int, c_int]),
+    "mg_griffin_lim": (c_int, [_P, _P, _P, _P, _P, c_size_t, c_int, c_int, c_float, _P]),
     "mg_swd_pyr_down": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "mg_swd_pyr_lap": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     "mg_swd_gather": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64, _P]),

@@ -8,7 +8,7 @@ from typing import Tuple
 import torch as th
 
 from . import constant, wavio
-from .. import ops
+from .. import gl_ops, ops
 
 _bark_cache = {}
 
@@ -135,7 +135,7 @@ def stft_to_stacked_phase_magn(complex_values: th.Tensor, nb_vec: int = constant
     return ops.codec_fwd(c, _bark_vector(c.shape[0], dev), nb_vec, stacked=True)
 
 
-def magn_phase_to_waveform(magn_phase: th.Tensor) -> th.Tensor:
+def _check_magn_phase(magn_phase: th.Tensor) -> None:
     assert len(magn_phase.size()) == 4, \
         f"(N, 2, H, W), actual = {magn_phase.size()}"
     assert magn_phase.size()[1] == 2, \
@@ -143,11 +143,46 @@ def magn_phase_to_waveform(magn_phase: th.Tensor) -> th.Tensor:
     assert magn_phase.size()[2] == constant.N_FFT // 2, \
         f"Frequency size must be equal to {constant.N_FFT // 2}, " \
         f"actual = {magn_phase.size()[2]}"
+
+
+def istft(complex_values: th.Tensor) -> th.Tensor:
+    """complex64 (512, T), T >= 4, Nyquist row dropped -> waveform [256 * (T - 1)]: the counterpart of `stft_from_waveform` for
+    1024 / 256 (`mg_istft_1024`, one launch)."""
+    if complex_values.dim() != 2 or complex_values.shape[0] != constant.N_FFT // 2 or complex_values.shape[1] < gl_ops.MIN_FRAMES:
+        raise ValueError(f"a ({constant.N_FFT // 2}, T >= {gl_ops.MIN_FRAMES}) spectrum expected, got {tuple(complex_values.shape)}")
+    dev = complex_values.device if complex_values.is_cuda else _device()
+    return gl_ops.istft_1024(complex_values.to(dev, th.complex64).contiguous())
+
+
+def griffin_lim(magn_phase: th.Tensor, n_iter: int = 32, momentum: float = 0.99, init: str = "phase", return_convergence: bool = False):
+    """(N, 2, 512, W) -> waveform [256 * (N W - 1)] after n_iter rounds of Griffin-Lim (torchaudio.functional.griffinlim with
+    power = 1 and rand_init = False): the decoded magnitude is held and the phase moves towards one that a signal can have.
+    init: "phase" starts from the decoded phase image (n_iter = 0 is `magn_phase_to_waveform` up to rounding), "zero" from zero
+    phase, i.e. from the magnitude alone.  return_convergence: also a float64 tensor [n_iter] on the device, entry k the relative
+    distance || |STFT(ISTFT(Z))| - M || / || M || at the start of round k."""
+    if init not in ("phase", "zero"):
+        raise ValueError(f"init must be 'phase' or 'zero', got {init!r}")
+    _check_magn_phase(magn_phase)
+    gl_ops.check_loop_arguments(n_iter, momentum, magn_phase.shape[0] * magn_phase.shape[3])
+    dev = magn_phase.device if magn_phase.is_cuda else _device()
+    mp = magn_phase.to(dev, th.float32).contiguous()
+    magn, z = gl_ops.codec_inv_spectrum(mp, _bark_vector(constant.N_FFT // 2, dev), zero_phase=init == "zero")
+    return gl_ops.griffin_lim(magn, z, n_iter, momentum, return_convergence=return_convergence)
+
+
+_griffin_lim = griffin_lim   # the keyword of the two functions below shadows the name
+
+
+def magn_phase_to_waveform(magn_phase: th.Tensor, griffin_lim: int = 0, momentum: float = 0.99) -> th.Tensor:
+    """griffin_lim: rounds of Griffin-Lim phase refinement from the decoded phase (0: none, the reference's single inversion)"""
+    _check_magn_phase(magn_phase)
+    if griffin_lim:
+        return _griffin_lim(magn_phase, n_iter=griffin_lim, momentum=momentum)
     dev = magn_phase.device if magn_phase.is_cuda else _device()
     mp = magn_phase.to(dev, th.float32).contiguous()
     return ops.codec_inv(mp, _bark_vector(constant.N_FFT // 2, dev))
 
 
-def magn_phase_to_wav(magn_phase: th.Tensor, wav_path: str, sample_rate: int):
-    raw_audio = magn_phase_to_waveform(magn_phase)
+def magn_phase_to_wav(magn_phase: th.Tensor, wav_path: str, sample_rate: int, griffin_lim: int = 0, momentum: float = 0.99):
+    raw_audio = magn_phase_to_waveform(magn_phase, griffin_lim=griffin_lim, momentum=momentum)
     wavio.save(wav_path, raw_audio[None, :], sample_rate)

@@ -404,13 +404,22 @@ __global__ void __launch_bounds__(576) inv_phase_cumsum(const float* __restrict_
   }
 }
 
+// MODE 0: Z alone (mg_codec_inv); 1: the magnitude M = m / range as well; 2: M and Z = M + 0i, the phase image unused
+// (mg_codec_inv_spectrum)
+template <int MODE>
 __global__ void __launch_bounds__(256) inv_polar(const float* __restrict__ acc, const float* __restrict__ m_in,
-                                                 const float* __restrict__ mm, float2* __restrict__ Z, size_t total) {
+                                                 const float* __restrict__ mm, float2* __restrict__ Z, float* __restrict__ M_out,
+                                                 size_t total) {
   const float range = mm[1] - mm[0];
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const float pm = py_mod(acc[i], TWO_PI_F);
     const float mag = m_in[i] / range;
-    Z[i] = make_float2(mag * cosf(pm), mag * sinf(pm));
+    if (MODE != 0) M_out[i] = mag;
+    if (MODE == 2) {
+      Z[i] = make_float2(mag, 0.f);
+    } else {
+      const float pm = py_mod(acc[i], TWO_PI_F);
+      Z[i] = make_float2(mag * cosf(pm), mag * sinf(pm));
+    }
   }
 }
 
@@ -522,6 +531,40 @@ extern "C" int mg_codec_fwd(const float* stft_c64, const float* bark_scale, floa
                               T, nb_vec, stream);
 }
 
+// The front half of the inverse codec, shared by mg_codec_inv and mg_codec_inv_spectrum: un-bark and min / max, the running phase,
+// polar -> complex.  m [NB][TT], run [NB][TT], part [2 * NB * 64], mm [2]: scratch; Z [NB][TT] complex; mode: inv_polar's MODE.
+static int codec_inv_front(const float* magn_phase, const float* bark_scale, float* m, float* run, float* part, float* mm, float2* Z,
+                           float* M_out, int mode, int N, int W, hipStream_t s) {
+  const int TT = N * W;
+  int gx = (TT + 255) / 256;
+  if (gx > 64) gx = 64;
+  hipLaunchKernelGGL(inv_unbark, dim3(gx, NB), dim3(256), 0, s, magn_phase, bark_scale, m, part, N, W);
+  hipLaunchKernelGGL(minmax_final, dim3(1), dim3(256), 0, s, part, gx * NB, mm);
+  if (mode != 2) {
+    static MgPerDevice once;  // the LDS limit is a per-device function attribute
+    if (mg_first_use_on_device(once)) {
+      const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&inv_phase_cumsum),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
+      if (ea != hipSuccess) {
+        mg_set_error("mg_codec_inv: hipFuncSetAttribute: %s", hipGetErrorString(ea));
+        return MG_ELAUNCH;
+      }
+    }
+    hipLaunchKernelGGL(inv_phase_cumsum, dim3(NB / 64), dim3(576), (size_t)4 * UTILE * sizeof(float), s, magn_phase, run, N, W);
+  }
+  const size_t total = (size_t)NB * TT;
+  int pb = (int)((total + 255) / 256);
+  if (pb > 8192) pb = 8192;
+  if (mode == 0)
+    hipLaunchKernelGGL(inv_polar<0>, dim3(pb), dim3(256), 0, s, run, m, mm, Z, M_out, total);
+  else if (mode == 1)
+    hipLaunchKernelGGL(inv_polar<1>, dim3(pb), dim3(256), 0, s, run, m, mm, Z, M_out, total);
+  else
+    hipLaunchKernelGGL(inv_polar<2>, dim3(pb), dim3(256), 0, s, run, m, mm, Z, M_out, total);
+  MG_CHECK_LAUNCH("mg_codec_inv(spectrum)");
+  return MG_OK;
+}
+
 extern "C" size_t mg_codec_inv_ws_bytes(int N, int W) {
   const size_t TT = (size_t)N * W;
   return ((size_t)NB * TT * 3 + TT * NFFT + 2 * (size_t)NB * 64 + 16) * sizeof(float);
@@ -542,27 +585,9 @@ extern "C" int mg_codec_inv(const float* magn_phase, const float* bark_scale, fl
   float* frames = m + (size_t)NB * TT * 3;
   float* part = frames + (size_t)TT * NFFT;
   float* mm = part + 2 * (size_t)NB * 64;
-  int gx = (TT + 255) / 256;
-  if (gx > 64) gx = 64;
-  hipLaunchKernelGGL(inv_unbark, dim3(gx, NB), dim3(256), 0, s, magn_phase, bark_scale, m, part, N, W);
-  hipLaunchKernelGGL(minmax_final, dim3(1), dim3(256), 0, s, part, gx * NB, mm);
-  static MgPerDevice once;  // the LDS limit is a per-device function attribute
-  if (mg_first_use_on_device(once)) {
-    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&inv_phase_cumsum),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
-    if (ea != hipSuccess) {
-      mg_set_error("mg_codec_inv: hipFuncSetAttribute: %s", hipGetErrorString(ea));
-      return MG_ELAUNCH;
-    }
-  }
   float* run = frames;  // running phase [NB][TT]: borrows the frame buffer (TT*1024 floats), which inv_frames fills afterwards
-  hipLaunchKernelGGL(inv_phase_cumsum, dim3(NB / 64), dim3(576), (size_t)4 * UTILE * sizeof(float), s, magn_phase, run, N, W);
-  {
-    const size_t total = (size_t)NB * TT;
-    int pb = (int)((total + 255) / 256);
-    if (pb > 8192) pb = 8192;
-    hipLaunchKernelGGL(inv_polar, dim3(pb), dim3(256), 0, s, run, m, mm, Z, total);
-  }
+  const int rc = codec_inv_front(magn_phase, bark_scale, m, run, part, mm, Z, nullptr, 0, N, W, s);
+  if (rc != MG_OK) return rc;
   hipLaunchKernelGGL(inv_frames, dim3(TT), dim3(256), 0, s, Z, frames, TT);
   const long long out_len = (long long)HOP * (TT - 1);
   int blocks = (int)((out_len + 255) / 256);
@@ -570,4 +595,27 @@ extern "C" int mg_codec_inv(const float* magn_phase, const float* bark_scale, fl
   hipLaunchKernelGGL(inv_overlap_add, dim3(blocks), dim3(256), 0, s, frames, wav_out, TT, out_len);
   MG_CHECK_LAUNCH("mg_codec_inv");
   return MG_OK;
+}
+
+extern "C" size_t mg_codec_inv_spectrum_ws_bytes(int N, int W) {
+  const size_t TT = (size_t)N * W;
+  return ((size_t)NB * TT * 2 + 2 * (size_t)NB * 64 + 16) * sizeof(float);
+}
+
+extern "C" int mg_codec_inv_spectrum(const float* magn_phase, const float* bark_scale, float* magn_out, float* z_c64, int zero_phase,
+                                     void* ws, size_t ws_bytes, int N, int W, mg_stream_t stream) {
+  MG_CHECK_ARG(magn_phase && bark_scale && magn_out && z_c64 && ws && N > 0 && W > 0, "mg_codec_inv_spectrum: bad arguments");
+  MG_CHECK_ARG((long long)N * W >= 2 && (long long)N * W < (1ll << 30), "mg_codec_inv_spectrum: needs 2 <= N * W < 2^30 frames");
+  MG_CHECK_ARG(reinterpret_cast<uintptr_t>(z_c64) % 8 == 0, "mg_codec_inv_spectrum: the spectrum must be 8-byte aligned");
+  if (ws_bytes < mg_codec_inv_spectrum_ws_bytes(N, W)) {
+    mg_set_error("mg_codec_inv_spectrum: workspace too small");
+    return MG_EWORKSPACE;
+  }
+  const size_t bins = (size_t)NB * N * W;
+  float* m = reinterpret_cast<float*>(ws);
+  float* run = m + bins;
+  float* part = run + bins;
+  float* mm = part + 2 * (size_t)NB * 64;
+  return codec_inv_front(magn_phase, bark_scale, m, run, part, mm, reinterpret_cast<float2*>(z_c64), magn_out, zero_phase ? 2 : 1, N,
+                         W, (hipStream_t)stream);
 }

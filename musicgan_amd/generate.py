@@ -20,9 +20,11 @@ def _load_generator(rand_channels: int, checkpoint: str, device: torch.device) -
 
 
 def generate(output_dir: str, rand_channels: int, gen_dict_state: str, nb_vec: int, nb_music: int,
-             audio_format: str = "wav") -> None:
+             audio_format: str = "wav", griffin_lim: int = 0) -> None:
     """audio_format: "wav" (32-bit float, the reference's output), "flac" (24-bit) or "ogg" (Ogg Vorbis at the default quality),
-    the last two encoded on the GPU"""
+    the last two encoded on the GPU; griffin_lim: rounds of Griffin-Lim phase refinement before the file is written (0: none)"""
+    if isinstance(griffin_lim, bool) or not isinstance(griffin_lim, int) or griffin_lim < 0:
+        raise ValueError(f"griffin_lim must be a non-negative integer, got {griffin_lim!r}")
     if audio_format not in ("wav", "flac", "ogg"):
         raise ValueError(f"audio_format must be 'ogg', 'wav' or 'flac', got {audio_format!r}")
     if os.path.exists(output_dir) and not os.path.isdir(output_dir):
@@ -40,4 +42,5 @@ def generate(output_dir: str, rand_channels: int, gen_dict_state: str, nb_vec: i
         # one item at a time: the level-7 activations of a 512 x (512 * nb_vec) image are ~1 GB each
         for idx, z in enumerate(latents.split(1, dim=0)):
             image = gen(z.contiguous(), 1.0)
-            audio.magn_phase_to_wav(image, os.path.join(output_dir, f"sound_{idx}.{audio_format}"), audio.SAMPLE_RATE)
+            audio.magn_phase_to_wav(image, os.path.join(output_dir, f"sound_{idx}.{audio_format}"), audio.SAMPLE_RATE,
+                                    **({"griffin_lim": griffin_lim} if griffin_lim else {}))
