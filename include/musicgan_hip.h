@@ -592,6 +592,21 @@ size_t mg_griffin_lim_ws_bytes(int TT, int n_iter);
 int mg_griffin_lim(const float* magn, float* z_c64, float* wav_out, double* convergence, void* ws, size_t ws_bytes, int TT,
                    int n_iter, float momentum, mg_stream_t stream);
 
+/* ------------------------------------------------------------------ phase vocoder (csrc/phasevocoder.hip)
+ * torchaudio.functional.phase_vocoder for spectra in mg_stft_1024's layout (512 x frames interleaved complex64, frequency-major,
+ * hop 256 of 1024) with a rational rate p / q in [1/8, 8] (above 1: faster and shorter); definition and precision: DESIGN.md.
+ * mg_phase_vocoder_len: host only; the output's frames ceil(frames q / p), or -1 for p < 1, q < 1, a rate outside [1/8, 8],
+ *   frames < 1 or frames p >= 2^62.
+ * mg_phase_vocoder_ws_bytes: host only; 8 bytes per input bin (|X| and arg X, float32) and one float64 per row and tile of 256
+ *   output frames; 0 for bad arguments or 2^31 frames and more on either side.
+ * mg_phase_vocoder: out_c64 [512][len] receives the re-timed spectrum.  |X| and arg X are torch's float32 values, everything between
+ *   them and the final sine / cosine is float64, the phase advance pi k / 2 per frame is applied modulo 2 pi as exact quarter turns
+ *   and only the wrapped deviations are summed, in a fixed order: the same bits on every run.  Four launches on `stream`, no
+ *   allocation, no synchronisation, no atomics: the call can be captured in a graph.  Spectra 8-byte aligned, ws 16-byte aligned. */
+int64_t mg_phase_vocoder_len(int64_t frames, int p, int q);
+size_t mg_phase_vocoder_ws_bytes(int64_t frames, int p, int q);
+int mg_phase_vocoder(const float* x_c64, float* out_c64, void* ws, size_t ws_bytes, int64_t frames, int p, int q, mg_stream_t stream);
+
 /* CRC-32 (zip / zlib) of the float64 widening of float32 samples: crc_out[i] = crc32 of the little-endian bytes of
  * x[i*floats_per_sample ...].astype(float64) -- the checksum the zip container of `th.save(sample.to(th.float64))`
  * [create_dataset.py:52-62] stores for its payload, which the reference's writer computes on one host core per sample.

@@ -3,6 +3,8 @@
 lazily (importing `train` pulls in the GPU library, `view_audio` pulls in matplotlib)."""
 import argparse
 import importlib
+import re
+from fractions import Fraction
 
 _METRICS = ("swd", "msssim", "nn")
 
@@ -14,13 +16,28 @@ def _metric_list(text: str):
     return names
 
 
+def _fraction_list(text: str):
+    """'9/10,1.1' -> (Fraction(9, 10), Fraction(11, 10)): a/b or decimals, taken exactly"""
+    try:
+        return tuple(Fraction(t.strip()) for t in text.split(","))
+    except (ValueError, ZeroDivisionError):
+        raise argparse.ArgumentTypeError(f"a comma-separated list of numbers (a/b or decimals) expected, got {text!r}")
+
+
 # mode -> (module, function, [(flags, kwargs)], lambda args: positional call arguments[, lambda args: keyword call arguments])
 _MODES = {
     "create_dataset": ("create_dataset", "create_dataset", [
         (("audio_path",), dict(type=str, help="can be /path/to/*.wav")),
         (("-o", "--output-dir"), dict(type=str, required=True, help="The folder where the tensor files will be saved")),
         (("--resample",), dict(action="store_true", help="resample files that are not at 44.1 kHz (else they are refused)")),
-    ], lambda a: (a.audio_path, a.output_dir), lambda a: {"resample": True} if a.resample else {}),
+        (("--stretch",), dict(type=_fraction_list, default=(), metavar="9/10,1.1",
+                              help="also write every file re-timed by these rates (a/b or decimals in [1/8, 8], above 1: faster) "
+                                   "at its own pitch: GPU phase vocoder")),
+        (("--pitch",), dict(type=_fraction_list, default=(), metavar="-1,1",
+                            help="also write every file transposed by these numbers of semitones at its own duration")),
+    ], lambda a: (a.audio_path, a.output_dir),
+        lambda a: {**({"resample": True} if a.resample else {}), **({"stretch": a.stretch} if a.stretch else {}),
+                   **({"pitch": a.pitch} if a.pitch else {})}),
     "train": ("train", "train", [
         (("run",), dict(type=str, metavar="RUN_NAME")),
         (("-o", "--out-path"), dict(dest="out_path", type=str, required=True)),
@@ -75,6 +92,8 @@ def build_parser() -> argparse.ArgumentParser:
         sub = modes.add_parser(mode)
         for flags, kwargs in arguments:
             sub.add_argument(*flags, **kwargs)
+        # argparse takes "-1" for a value and "-1,1" for an unknown flag: lists of numbers are values too (`--pitch -1,1`)
+        sub._negative_number_matcher = re.compile(r"^-\d[\d.,/-]*$|^-\.\d[\d.,/-]*$")
     return parser
 
 

@@ -193,6 +193,9 @@ SIGNATURES = {
     "mg_istft_1024": (c_int, [_P, _P, c_int, _P]),
     "mg_griffin_lim_ws_bytes": (c_size_t, [c_int, c_int]),
     "mg_griffin_lim": (c_int, [_P, _P, _P, _P, _P, c_size_t, c_int, c_int, c_float, _P]),
+    "mg_phase_vocoder_len": (c_int64, [c_int64, c_int, c_int]),
+    "mg_phase_vocoder_ws_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "mg_phase_vocoder": (c_int, [_P, _P, _P, c_size_t, c_int64, c_int, c_int, _P]),
     "mg_swd_pyr_down": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "mg_swd_pyr_lap": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     "mg_swd_gather": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64, _P]),

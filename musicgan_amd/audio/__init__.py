@@ -1,7 +1,8 @@
 """Public surface of the reference's `audio` package (/root/reference/music_gan/audio/__init__.py) plus the two
 waveform-level helpers the drivers use (`stft_from_waveform`, `magn_phase_to_waveform`), `resample`
 (torchaudio.functional.resample, what the reference's users call for files that are not at 44.1 kHz), `istft` (the inverse of
-`stft_from_waveform`) and `griffin_lim` (torchaudio.functional.griffinlim on a magnitude / phase image)."""
+`stft_from_waveform`), `griffin_lim` (torchaudio.functional.griffinlim on a magnitude / phase image) and `phase_vocoder`,
+`time_stretch`, `pitch_shift` (torchaudio.functional's, with a rational rate; `pitch_ratio` is the fraction a pitch stands for)."""
 from . import constant as _constant
 from . import functions as _functions
 from .constant import N_FFT, N_VEC, SAMPLE_RATE, STFT_STRIDE
@@ -9,9 +10,11 @@ from .dataset import AudioDataset, PackedAudioDataset, PackedLoader, has_packed,
 from .transforms import ChangeRange, ChannelMinMaxNorm
 
 for _name in ("wav_to_stft", "stft_to_phase_magn", "magn_phase_to_wav", "bark_magn_scale", "stft_from_waveform",
-              "magn_phase_to_waveform", "stft_to_stacked_phase_magn", "resample", "istft", "griffin_lim"):
+              "magn_phase_to_waveform", "stft_to_stacked_phase_magn", "resample", "istft", "griffin_lim", "phase_vocoder", "time_stretch",
+              "pitch_shift", "pitch_ratio"):
     globals()[_name] = getattr(_functions, _name)
 del _name
 
 __all__ = ["wav_to_stft", "stft_to_phase_magn", "magn_phase_to_wav", "bark_magn_scale", "stft_from_waveform",
-           "magn_phase_to_waveform", "stft_to_stacked_phase_magn", "resample", "istft", "griffin_lim", "AudioDataset", "PackedAudioDataset", "PackedLoader", "has_packed", "write_packed", "ChannelMinMaxNorm", "ChangeRange", *_constant.__all__]
+           "magn_phase_to_waveform", "stft_to_stacked_phase_magn", "resample", "istft", "griffin_lim", "phase_vocoder", "time_stretch",
+           "pitch_shift", "pitch_ratio", "AudioDataset", "PackedAudioDataset", "PackedLoader", "has_packed", "write_packed", "ChannelMinMaxNorm", "ChangeRange", *_constant.__all__]

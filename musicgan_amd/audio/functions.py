@@ -3,12 +3,13 @@
 `mg_codec_inv` on the current ROCm device.  Results come back as tensors on that device."""
 from __future__ import annotations
 
+from fractions import Fraction
 from typing import Tuple
 
 import torch as th
 
 from . import constant, wavio
-from .. import gl_ops, ops
+from .. import gl_ops, ops, pv_ops
 
 _bark_cache = {}
 
@@ -152,6 +153,54 @@ def istft(complex_values: th.Tensor) -> th.Tensor:
         raise ValueError(f"a ({constant.N_FFT // 2}, T >= {gl_ops.MIN_FRAMES}) spectrum expected, got {tuple(complex_values.shape)}")
     dev = complex_values.device if complex_values.is_cuda else _device()
     return gl_ops.istft_1024(complex_values.to(dev, th.complex64).contiguous())
+
+
+def phase_vocoder(complex_specgrams: th.Tensor, rate) -> th.Tensor:
+    """torchaudio.functional.phase_vocoder for this package's STFT (1024 / 256, phase_advance pi k / 2): complex (512, T), T >= 1 ->
+    complex64 (512, ceil(T / rate)) on the device; a CPU tensor is moved there first.  rate (above 1: faster and shorter) is an int,
+    a fractions.Fraction or a float in [1/8, 8]; a float is turned into Fraction(rate).limit_denominator(1000), so that the time axis
+    is integer arithmetic.  Magnitudes and angles are float32, the phase is accumulated in float64 modulo 2 pi."""
+    r = pv_ops.as_rate(rate)
+    if complex_specgrams.dim() != 2 or complex_specgrams.shape[0] != constant.N_FFT // 2 or complex_specgrams.shape[1] < 1:
+        raise ValueError(f"a ({constant.N_FFT // 2}, T >= 1) spectrum expected, got {tuple(complex_specgrams.shape)}")
+    if not complex_specgrams.is_complex():
+        raise ValueError(f"a complex spectrum expected, got {complex_specgrams.dtype}")
+    dev = complex_specgrams.device if complex_specgrams.is_cuda else _device()
+    return pv_ops.phase_vocoder(complex_specgrams.to(dev, th.complex64).contiguous(), r.numerator, r.denominator)
+
+
+def time_stretch(waveform: th.Tensor, rate) -> th.Tensor:
+    """mono (samples,) float waveform -> the same sound `rate` times as fast at the same pitch: `istft(phase_vocoder(
+    stft_from_waveform(waveform), rate))`, 256 * (n - 1) samples for n = ceil((1 + samples // 256) / rate) frames; n < 4 raises
+    the ValueError of `istft`.  rate: as `phase_vocoder` takes it."""
+    r = pv_ops.as_rate(rate)
+    if waveform.dim() != 1 or not waveform.is_floating_point():
+        raise ValueError(f"a mono floating-point waveform (samples,) expected, got {tuple(waveform.shape)} {waveform.dtype}")
+    return istft(phase_vocoder(stft_from_waveform(waveform), r))
+
+
+def pitch_ratio(n_steps) -> Fraction:
+    """the frequency ratio 2^(n_steps / 12) of n_steps semitones as the closest fraction P / Q with Q <= 64 (host arithmetic; at
+    most 1.955 cents off for every whole n_steps in -12 .. 12)"""
+    if isinstance(n_steps, bool) or not isinstance(n_steps, (int, float, Fraction)) or float(n_steps) != float(n_steps):
+        raise ValueError(f"n_steps must be a number of semitones, got {n_steps!r}")
+    return Fraction(2 ** (float(n_steps) / 12)).limit_denominator(64)
+
+
+def pitch_shift(waveform: th.Tensor, n_steps, sample_rate: int = constant.SAMPLE_RATE) -> th.Tensor:
+    """torchaudio.functional.pitch_shift for a mono (samples,) waveform: with P / Q = pitch_ratio(n_steps), `time_stretch` by Q / P
+    (longer for an upward shift), then `resample` from P to Q, cropped or zero-padded to the input's length.  The result does not
+    depend on `sample_rate` (kept for torchaudio's signature)."""
+    f = pitch_ratio(n_steps)
+    pv_ops.as_rate(1 / f)
+    y = time_stretch(waveform, 1 / f)
+    y = resample(y, f.numerator, f.denominator)
+    n = waveform.shape[0]
+    if y.shape[0] >= n:
+        return y[:n]
+    out = th.zeros((n,), dtype=y.dtype, device=y.device)
+    out[:y.shape[0]] = y
+    return out
 
 
 def griffin_lim(magn_phase: th.Tensor, n_iter: int = 32, momentum: float = 0.99, init: str = "phase", return_convergence: bool = False):

@@ -13,6 +13,9 @@ loader (audio/dataset.py) is streamed out of the same pinned chunks instead of r
 `resample=True` accepts files at any sample rate: their PCM is resampled to 44.1 kHz on the device (ops.resample_pcm, the
 torchaudio.functional.resample a user of the reference calls first) in the launch that also normalises it; 44.1 kHz files take the
 unchanged path.
+`stretch` / `pitch` add re-timed and transposed copies of every file behind its own samples (audio.phase_vocoder on the file's STFT;
+for a pitch, the mono signal resampled by P / Q first and re-timed by Q / P, which restores the duration): the remedy for a small
+corpus.  Without them nothing changes.
 """
 import glob
 import json
@@ -46,6 +49,43 @@ def host_cpus() -> int:
 def _nb_samples(nb_frames_wav: int, nb_vec: int) -> int:
     t = 1 + nb_frames_wav // audio.STFT_STRIDE
     return 0 if t < nb_vec else (t - 1) // nb_vec
+
+
+def check_variants(stretch=(), pitch=()):
+    """-> (stretch rates as Fractions, [(pitch value, P / Q)]); ValueError for a rate outside [1/8, 8], a rate of exactly 1 or a
+    pitch of exactly 0 (each would duplicate the original) and duplicate entries -- host arithmetic, no device needed"""
+    from . import pv_ops
+    rates = [pv_ops.as_rate(r) for r in stretch]
+    if any(r == 1 for r in rates):
+        raise ValueError("a stretch rate of 1 would duplicate the original")
+    if len(set(rates)) != len(rates):
+        raise ValueError(f"duplicate stretch rates: {[str(r) for r in rates]}")
+    ratios = []
+    for v in pitch:
+        f = audio.pitch_ratio(v)
+        if float(v) == 0 or f == 1:
+            raise ValueError(f"a pitch of {v} semitones would duplicate the original")
+        pv_ops.as_rate(1 / f)
+        ratios.append((v, f))
+    if len({float(v) for v, _ in ratios}) != len(ratios) or len({f for _, f in ratios}) != len(ratios):
+        raise ValueError(f"duplicate pitch values: {[str(v) for v, _ in ratios]}")
+    return tuple(rates), tuple(ratios)
+
+
+def variant_counts(nb_frames_wav: int, nb_vec: int, rates=(), ratios=()) -> list:
+    """samples of a file of nb_frames_wav frames at 44.1 kHz and of each of its variants, in the order they are written: host
+    arithmetic on the length alone (what the global numbering under torchrun rests on)"""
+    from . import ops, pv_ops
+
+    def of_frames(t):
+        return 0 if t < nb_vec else (t - 1) // nb_vec
+    t0 = 1 + nb_frames_wav // audio.STFT_STRIDE
+    out = [_nb_samples(nb_frames_wav, nb_vec)]
+    out += [of_frames(pv_ops.phase_vocoder_len(t0, r.numerator, r.denominator)) for r in rates]
+    for _, f in ratios:
+        t1 = 1 + ops.resample_len(nb_frames_wav, f.numerator, f.denominator) // audio.STFT_STRIDE
+        out.append(of_frames(pv_ops.phase_vocoder_len(t1, f.denominator, f.numerator)))
+    return out
 
 
 def _remove_sidecar(folder: str) -> None:
@@ -289,10 +329,14 @@ class _Chunk:
 
 
 def create_dataset(audio_path: str, dataset_output_dir: str, *, packed: bool = True, writer_threads: int = 0,
-                   stats: dict = None, resample: bool = False) -> None:
+                   stats: dict = None, resample: bool = False, stretch=(), pitch=()) -> None:
     """`packed` (extension, single-process runs): also write the float32 memory-mapped side-car the fast loader reads
     (audio/dataset.py); the reference-format `magn_phase_{idx}.pt` files are written either way.  `writer_threads`: 0 = one per
-    available CPU (at most 16).  `resample`: files not at 44.1 kHz are resampled to it (else they raise, as in the reference)."""
+    available CPU (at most 16).  `resample`: files not at 44.1 kHz are resampled to it (else they raise, as in the reference).
+    `stretch`: rates (int, Fraction or float, as audio.phase_vocoder takes them; above 1: faster); `pitch`: semitones.  Behind its own
+    samples every file also yields, in the order given, those of its STFT re-timed by each rate, then those of its mono 44.1 kHz
+    signal resampled by P / Q = audio.pitch_ratio(value) and re-timed by Q / P."""
+    rates, ratios = check_variants(stretch, pitch)
     w_p = glob.glob(audio_path)
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:
@@ -312,7 +356,7 @@ def create_dataset(audio_path: str, dataset_output_dir: str, *, packed: bool = T
             if resample and sr != audio.SAMPLE_RATE:  # the samples come from the resampled signal: ceil(44100 L / sr) frames
                 from . import ops
                 frames = ops.resample_len(frames, sr, audio.SAMPLE_RATE)
-            counts.append(_nb_samples(frames, nb_vec))
+            counts.append(sum(variant_counts(frames, nb_vec, rates, ratios)) if rates or ratios else _nb_samples(frames, nb_vec))
     t_setup = time.perf_counter()
     mine = [f_i for f_i in range(len(w_p)) if world == 1 or f_i % world == rank]
     first_idx = {}
@@ -372,54 +416,68 @@ def create_dataset(audio_path: str, dataset_output_dir: str, *, packed: bool = T
             th.cuda.current_stream().wait_event(ready)  # the upload (loader's stream) is ordered in front of the STFT
             pcm.record_stream(th.cuda.current_stream())
             complex_values = audio.functions.stft_from_pcm(pcm, nperseg=audio.N_FFT, stride=audio.STFT_STRIDE, sample_rate=sr)
-            del pcm
+            if not ratios:
+                del pcm
             t1 = time.perf_counter()
             t_load += t1 - t0
-            # create_dataset.py:41-42 skips files of fewer than nb_vec frames; a file of EXACTLY nb_vec frames has nb_vec - 1 phase
-            # differences, i.e. no complete image either (the reference would write one degenerate (2, 512, 0) tensor for it)
-            if complex_values.size()[1] - 1 < nb_vec:
-                continue
-            both = audio.stft_to_stacked_phase_magn(complex_values, nb_vec=nb_vec)  # (S, 2, 512, nb_vec) float32, on the device
-            n_files += 1
-            crcs = None
-            if template is not None:
-                from . import ops
-                crcs = ops.crc32_of_float64(both)  # int64 [S] on the device; it travels with the samples, no host sync here
-            produced = th.cuda.Event()
-            produced.record()  # codec (+ CRC) of this file queued: the copy streams start behind it
-            for c0 in range(0, both.size()[0], CHUNK_SAMPLES):
-                t2 = time.perf_counter()
-                chunk = ring.get()
-                t_wait += time.perf_counter() - t2
-                n = min(CHUNK_SAMPLES, both.size()[0] - c0)
-                chunk.acquire()  # held by this loop until everything that reads the chunk has been queued
-                cs = copy_streams[n_chunks % 2]
-                n_chunks += 1
-                with th.cuda.stream(cs):
-                    cs.wait_event(produced)
-                    chunk.host[:n].copy_(both[c0:c0 + n], non_blocking=True)
-                    if crcs is not None:
-                        chunk.crc[:n].copy_(crcs[c0:c0 + n], non_blocking=True)
-                        crcs.record_stream(cs)
-                    both.record_stream(cs)
-                    chunk.event.record(cs)
-                r0 = 0
-                while r0 < n:
-                    # a job = consecutive rows of this chunk inside ONE block of side-car rows (global row = len(names); rows in idx
-                    # order == AudioDataset order only after the sort in _finish_sidecar)
-                    g_row = len(names)
-                    m = min(n - r0, _ds.PACKED_BLOCK_ROWS - g_row % _ds.PACKED_BLOCK_ROWS)
-                    batch = [f"magn_phase_{idx + k}.pt" for k in range(m)]
-                    fd, off = None, 0
-                    if side is not None:
-                        k_sh, local = _ds.shard_of_row(g_row, _ds.PACKED_SHARDS, _ds.PACKED_BLOCK_ROWS)
-                        fd, off = side[k_sh], local * row_bytes
-                    writers.submit(chunk, r0, [join(dataset_output_dir, b) for b in batch], fd, off,
-                                   check_first=crcs is not None and c0 + r0 == 0)
-                    names.extend(batch)
-                    idx += m
-                    r0 += m
-                chunk.release()
+            spectra = [complex_values]
+            if rates or ratios:  # the variants of this file, from the spectrum and the PCM that are on the device already
+                from . import ops, pv_ops
+                spectra += [pv_ops.phase_vocoder(complex_values, r.numerator, r.denominator) for r in rates]
+                if ratios:
+                    mono = ops.pcm_to_mono(pcm) if sr == audio.SAMPLE_RATE else ops.resample_pcm(pcm, sr, audio.SAMPLE_RATE)
+                    del pcm
+                    for _, f in ratios:
+                        shifted = ops.stft_1024(ops.resample_rows(mono[None, :], f.numerator, f.denominator)[0].contiguous())
+                        spectra.append(pv_ops.phase_vocoder(shifted, f.denominator, f.numerator))
+                    del mono
+            del complex_values
+            for v_i, complex_values in enumerate(spectra):
+                # create_dataset.py:41-42 skips files of fewer than nb_vec frames; a file of EXACTLY nb_vec frames has nb_vec - 1 phase
+                # differences, i.e. no complete image either (the reference would write one degenerate (2, 512, 0) tensor for it)
+                if complex_values.size()[1] - 1 < nb_vec:
+                    continue  # (a variant that is too short is left out in the same way)
+                both = audio.stft_to_stacked_phase_magn(complex_values, nb_vec=nb_vec)  # (S, 2, 512, nb_vec) float32, on the device
+                n_files += v_i == 0
+                crcs = None
+                if template is not None:
+                    from . import ops
+                    crcs = ops.crc32_of_float64(both)  # int64 [S] on the device; it travels with the samples, no host sync here
+                produced = th.cuda.Event()
+                produced.record()  # codec (+ CRC) of this file queued: the copy streams start behind it
+                for c0 in range(0, both.size()[0], CHUNK_SAMPLES):
+                    t2 = time.perf_counter()
+                    chunk = ring.get()
+                    t_wait += time.perf_counter() - t2
+                    n = min(CHUNK_SAMPLES, both.size()[0] - c0)
+                    chunk.acquire()  # held by this loop until everything that reads the chunk has been queued
+                    cs = copy_streams[n_chunks % 2]
+                    n_chunks += 1
+                    with th.cuda.stream(cs):
+                        cs.wait_event(produced)
+                        chunk.host[:n].copy_(both[c0:c0 + n], non_blocking=True)
+                        if crcs is not None:
+                            chunk.crc[:n].copy_(crcs[c0:c0 + n], non_blocking=True)
+                            crcs.record_stream(cs)
+                        both.record_stream(cs)
+                        chunk.event.record(cs)
+                    r0 = 0
+                    while r0 < n:
+                        # a job = consecutive rows of this chunk inside ONE block of side-car rows (global row = len(names); rows in idx
+                        # order == AudioDataset order only after the sort in _finish_sidecar)
+                        g_row = len(names)
+                        m = min(n - r0, _ds.PACKED_BLOCK_ROWS - g_row % _ds.PACKED_BLOCK_ROWS)
+                        batch = [f"magn_phase_{idx + k}.pt" for k in range(m)]
+                        fd, off = None, 0
+                        if side is not None:
+                            k_sh, local = _ds.shard_of_row(g_row, _ds.PACKED_SHARDS, _ds.PACKED_BLOCK_ROWS)
+                            fd, off = side[k_sh], local * row_bytes
+                        writers.submit(chunk, r0, [join(dataset_output_dir, b) for b in batch], fd, off,
+                                       check_first=crcs is not None and c0 + r0 == 0)
+                        names.extend(batch)
+                        idx += m
+                        r0 += m
+                    chunk.release()
             t_gpu += time.perf_counter() - t1
         t_loader = loader.busy_s
         t_drain = time.perf_counter()
