@@ -607,6 +607,40 @@ int64_t mg_phase_vocoder_len(int64_t frames, int p, int q);
 size_t mg_phase_vocoder_ws_bytes(int64_t frames, int p, int q);
 int mg_phase_vocoder(const float* x_c64, float* out_c64, void* ws, size_t ws_bytes, int64_t frames, int p, int q, mg_stream_t stream);
 
+/* ------------------------------------------------------------------ loudness and true peak (csrc/loudness.hip)
+ * Programme loudness after ITU-R BS.1770-4 / EBU R128 of a waveform x: C <= 8 rows of L float32 samples, `row_stride` floats apart
+ * (definitions: DESIGN.md).  seg = the samples of 100 ms; nseg = L / seg whole segments, the tail is dropped.
+ * mg_loudness_chunk: host only; the samples per chunk of the carried filter state.
+ * mg_loudness_ws_bytes: host only; four float64 per channel and chunk and one per channel, chunk and segment; 0 for bad arguments.
+ * mg_loudness_energy: S [C][nseg] float64 receives the sum of squares of the K-weighted channel over every segment.  coef is a HOST
+ *   array of ten float64: b0 b1 b2 a1 a2 of the shelf stage, then of the high-pass stage (a0 = 1); the filter starts from zero state
+ *   at sample 0.  States, products and sums are float64; the filtered signal is never written.  Four launches (zero-state end state
+ *   of every chunk, the carry s <- A^CHUNK s + z along each channel, the chunks again from their true state, the segments), no
+ *   atomics, one order for every sum: the same bits on every run.  nseg == 0: nothing is launched.  ws 16-byte aligned.
+ * mg_loudness_gate: weights is a HOST array of C finite non-negative float64.  Block i = segments i .. i + 3, z_i = sum_c
+ *   weights[c] (S[c][i] + .. + S[c][i+3]) / (4 seg), l_i = -0.691 + 10 log10 z_i.  record [4] float64 receives: the integrated
+ *   loudness -0.691 + 10 log10(mean z over the blocks with l_i > -70 and l_i > G), G = -0.691 + 10 log10(mean z over the blocks
+ *   with l_i > -70) - 10, or -inf when nseg < 4 or no block passes -70; max l_i (-inf when nseg < 4); the number of blocks above
+ *   -70; the number above both gates.  One launch of one workgroup.
+ * mg_true_peak_ws_bytes: host only; one float32 per channel and 2048 samples; 0 for bad arguments.
+ * mg_true_peak: peak [1] float32 receives max over channels and samples of max(|x|, |u|), linear, u = x interpolated 4x by the bank
+ *   of mg_resample_bank(1, 4, 6, 0.99) (`bank`, on the device) with zeros beyond both ends: the values mg_resample_pcm writes, bit
+ *   for bit, reduced without being written.  L >= 1.  Two launches.
+ * mg_loudness_normalize: gain [1] float32 receives min(10^((target - record[0]) / 20), 10^(ceiling / 20) / peak[0]) computed in
+ *   float64 and rounded once, 1 where record[0] = -inf; out [n] = x [n] * gain (contiguous).  Two launches; record, peak and gain
+ *   are device memory.
+ * Everything runs on `stream`, allocates nothing and synchronises nothing. */
+int mg_loudness_chunk(void);
+size_t mg_loudness_ws_bytes(int C, int64_t L, int seg);
+int mg_loudness_energy(const float* x, int C, int64_t L, int64_t row_stride, int seg, const double* coef, double* S, void* ws,
+                       size_t ws_bytes, mg_stream_t stream);
+int mg_loudness_gate(const double* S, const double* weights, int C, int64_t nseg, int seg, double* record, mg_stream_t stream);
+size_t mg_true_peak_ws_bytes(int C, int64_t L);
+int mg_true_peak(const float* x, int C, int64_t L, int64_t row_stride, const void* bank, size_t bank_bytes, float* peak, void* ws,
+                 size_t ws_bytes, mg_stream_t stream);
+int mg_loudness_normalize(const float* x, float* out, int64_t n, const double* record, const float* peak, double target,
+                          double ceiling, float* gain, mg_stream_t stream);
+
 /* CRC-32 (zip / zlib) of the float64 widening of float32 samples: crc_out[i] = crc32 of the little-endian bytes of
  * x[i*floats_per_sample ...].astype(float64) -- the checksum the zip container of `th.save(sample.to(th.float64))`
  * [create_dataset.py:52-62] stores for its payload, which the reference's writer computes on one host core per sample.

@@ -1,5 +1,5 @@
 """`python -m musicgan_amd <mode> ...`: the reference's four sub-commands with its positional names and flags
-(/root/reference/music_gan/__main__.py:11-124) and `evaluate`, which the reference does not have, declared as data and dispatched
+(/root/reference/music_gan/__main__.py:11-124) and `evaluate` and `loudness`, which the reference does not have, declared as data and dispatched
 lazily (importing `train` pulls in the GPU library, `view_audio` pulls in matplotlib)."""
 import argparse
 import importlib
@@ -57,9 +57,16 @@ _MODES = {
                                   "encoded on the GPU)")),
         (("--griffin-lim",), dict(dest="griffin_lim", type=int, default=0, metavar="N",
                                   help="N rounds of Griffin-Lim phase refinement before the file is written (default 0: none)")),
+        (("--loudness",), dict(type=float, default=None, metavar="LUFS",
+                               help="bring every file to this integrated loudness (ITU-R BS.1770-4), e.g. -14 (default: the level "
+                                    "the codec gives)")),
+        (("--true-peak",), dict(dest="true_peak", type=float, default=None, metavar="DBTP",
+                                help="true-peak ceiling of --loudness in dBTP (default -1)")),
     ], lambda a: (a.output_dir, a.rand_channels, a.gen_dict_state, a.nb_vec, a.nb_music),
         lambda a: {**({"audio_format": a.audio_format} if a.audio_format != "wav" else {}),
-                   **({"griffin_lim": a.griffin_lim} if a.griffin_lim else {})}),
+                   **({"griffin_lim": a.griffin_lim} if a.griffin_lim else {}),
+                   **({"loudness": a.loudness} if a.loudness is not None else {}),
+                   **({"peak_dbtp": a.true_peak} if a.true_peak is not None else {})}),
     "view_audio": ("view_audio", "view_audio", [
         (("--input-audio",), dict(type=str, required=True)),
         (("--image-idx",), dict(type=int, required=True)),
@@ -82,13 +89,20 @@ _MODES = {
         lambda a: dict(level=a.level, nb_images=a.nb_images, batch_size=a.batch_size, seed=a.seed, output=a.output,
                        **({"metrics": a.metrics} if a.metrics is not None else {}))),
 }
+# sub-commands that work on audio files, not on a model (same declaration; kept apart from the five modes above)
+_FILE_MODES = {
+    "loudness": ("loudness", "loudness", [
+        (("audio_path",), dict(type=str, help="can be /path/to/*.wav (any format that can be read: wav, aiff, au, flac, ogg)")),
+        (("-o", "--output"), dict(type=str, default=None, help="also write the measurements as JSON to this file")),
+    ], lambda a: (a.audio_path,), lambda a: {"output": a.output} if a.output is not None else {}),
+}
 
 
 def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser("MusicGAN")
     modes = parser.add_subparsers(dest="mode")
     modes.required = True
-    for mode, (_, _, arguments, *_) in _MODES.items():
+    for mode, (_, _, arguments, *_) in {**_MODES, **_FILE_MODES}.items():
         sub = modes.add_parser(mode)
         for flags, kwargs in arguments:
             sub.add_argument(*flags, **kwargs)
@@ -99,7 +113,7 @@ def build_parser() -> argparse.ArgumentParser:
 
 def main(argv=None) -> None:
     args = build_parser().parse_args(argv)
-    module, function, _, call_args, *call_kwargs = _MODES[args.mode]
+    module, function, _, call_args, *call_kwargs = {**_MODES, **_FILE_MODES}[args.mode]
     kwargs = call_kwargs[0](args) if call_kwargs else {}
     getattr(importlib.import_module(f".{module}", __package__), function)(*call_args(args), **kwargs)
 

@@ -196,6 +196,13 @@ SIGNATURES = {
     "mg_phase_vocoder_len": (c_int64, [c_int64, c_int, c_int]),
     "mg_phase_vocoder_ws_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "mg_phase_vocoder": (c_int, [_P, _P, _P, c_size_t, c_int64, c_int, c_int, _P]),
+    "mg_loudness_chunk": (c_int, []),
+    "mg_loudness_ws_bytes": (c_size_t, [c_int, c_int64, c_int]),
+    "mg_loudness_energy": (c_int, [_P, c_int, c_int64, c_int64, c_int, POINTER(ctypes.c_double), _P, _P, c_size_t, _P]),
+    "mg_loudness_gate": (c_int, [_P, POINTER(ctypes.c_double), c_int, c_int64, c_int, _P, _P]),
+    "mg_true_peak_ws_bytes": (c_size_t, [c_int, c_int64]),
+    "mg_true_peak": (c_int, [_P, c_int, c_int64, c_int64, _P, c_size_t, _P, _P, c_size_t, _P]),
+    "mg_loudness_normalize": (c_int, [_P, _P, c_int64, _P, _P, ctypes.c_double, ctypes.c_double, _P, _P]),
     "mg_swd_pyr_down": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "mg_swd_pyr_lap": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     "mg_swd_gather": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64, _P]),

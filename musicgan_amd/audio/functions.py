@@ -9,7 +9,7 @@ from typing import Tuple
 import torch as th
 
 from . import constant, wavio
-from .. import gl_ops, ops, pv_ops
+from .. import gl_ops, loud_ops, ops, pv_ops
 
 _bark_cache = {}
 
@@ -222,16 +222,89 @@ def griffin_lim(magn_phase: th.Tensor, n_iter: int = 32, momentum: float = 0.99,
 _griffin_lim = griffin_lim   # the keyword of the two functions below shadows the name
 
 
-def magn_phase_to_waveform(magn_phase: th.Tensor, griffin_lim: int = 0, momentum: float = 0.99) -> th.Tensor:
-    """griffin_lim: rounds of Griffin-Lim phase refinement from the decoded phase (0: none, the reference's single inversion)"""
+def kweighting_coefficients(sample_rate: int):
+    """((b, a), (b, a)): the shelf and the high-pass biquad of the K-weighting filter (ITU-R BS.1770-4) at `sample_rate`, each a
+    float64 array of three numbers (a[0] = 1), computed on the host from the analog prototypes libebur128 and pyloudnorm use; at
+    48 kHz the standard's table."""
+    import numpy as np
+    return tuple((np.asarray(b, dtype=np.float64), np.asarray(a, dtype=np.float64))
+                 for b, a in loud_ops.kweighting_coefficients(sample_rate))
+
+
+def _loudness_input(waveform: th.Tensor, min_length: int = 0) -> th.Tensor:
+    """(L,) or (C <= 8, L) float -> float32 (C, L) on the device with unit stride along L; ValueError before the device is touched"""
+    if not isinstance(waveform, th.Tensor) or waveform.dim() not in (1, 2):
+        raise ValueError(f"a waveform (samples,) or (channels, samples) expected, got {getattr(waveform, 'shape', waveform)!r}")
+    x = waveform[None, :] if waveform.dim() == 1 else waveform
+    loud_ops.check_waveform(x)
+    if x.shape[1] < min_length:
+        raise ValueError(f"at least one sample expected, got {tuple(waveform.shape)}")
+    dev = x.device if x.is_cuda else _device()
+    x = x.to(dev, th.float32)
+    return x.contiguous() if x.shape[1] > 1 and x.stride(1) != 1 else x
+
+
+def loudness(waveform: th.Tensor, sample_rate: int, channel_weights=None, return_details: bool = False):
+    """Integrated programme loudness in LUFS (ITU-R BS.1770-4 / EBU R128) of a float waveform (L,) or (C <= 8, L): K-weighting,
+    400 ms blocks every 100 ms, the absolute gate at -70 LUFS and the relative gate 10 LU below the mean of what passed.  A float64
+    0-dim tensor on the device (a CPU tensor is moved there first); -inf for less than 400 ms or when no block passes -70 LUFS.
+    channel_weights: one per channel (default 1.0 each; BS.1770 gives the surround channels 1.41).  return_details: also the
+    momentary maximum in LUFS and the numbers of blocks above the absolute gate and above both, as float64 0-dim tensors."""
+    loud_ops.check_sample_rate(sample_rate)
+    if not isinstance(waveform, th.Tensor) or waveform.dim() not in (1, 2):
+        raise ValueError(f"a waveform (samples,) or (channels, samples) expected, got {getattr(waveform, 'shape', waveform)!r}")
+    weights = loud_ops.check_weights(channel_weights, 1 if waveform.dim() == 1 else waveform.shape[0])
+    x = _loudness_input(waveform)
+    record = loud_ops.gate(loud_ops.segment_energies(x, sample_rate), sample_rate, weights)
+    return (record[0], record[1], record[2], record[3]) if return_details else record[0]
+
+
+def true_peak(waveform: th.Tensor) -> th.Tensor:
+    """The largest magnitude, linear, among the samples of a float waveform (L,) or (C <= 8, L), L >= 1, and the points between
+    them: the waveform interpolated 4x with the bank of `resample(waveform, 1, 4)` (Hann-windowed sinc, 4 phases of 15 taps, zeros
+    beyond both ends).  A float32 0-dim tensor on the device; 20 log10 of it is dBTP."""
+    return loud_ops.true_peak(_loudness_input(waveform, min_length=1))
+
+
+def normalize_loudness(waveform: th.Tensor, sample_rate: int, target_lufs: float = -14.0, peak_dbtp: float = -1.0,
+                       return_gain: bool = False):
+    """waveform * gain in float32 on the device, in the waveform's shape, with one gain for all channels:
+    gain = min(10^((target_lufs - loudness) / 20), 10^(peak_dbtp / 20) / true_peak) -- the target loudness unless the true-peak
+    ceiling binds first; 1 where the loudness is -inf.  The gain is computed in float64 on the device, rounded once to float32 and
+    never visits the host.  return_gain: also the gain, a float32 0-dim tensor on the device."""
+    loud_ops.check_sample_rate(sample_rate)
+    loud_ops.check_targets(target_lufs, peak_dbtp)
+    x = _loudness_input(waveform)
+    if x.shape[1] < 1:
+        out, gain = x.clone(), th.ones((), dtype=th.float32, device=x.device)
+    else:
+        x = x.contiguous()
+        record = loud_ops.gate(loud_ops.segment_energies(x, sample_rate), sample_rate)
+        out, gain = loud_ops.normalize(x, record, loud_ops.true_peak(x), target_lufs, peak_dbtp)
+    out = out.reshape(waveform.shape)
+    return (out, gain) if return_gain else out
+
+
+def magn_phase_to_waveform(magn_phase: th.Tensor, griffin_lim: int = 0, momentum: float = 0.99, loudness=None,
+                           peak_dbtp: float = -1.0, sample_rate: int = constant.SAMPLE_RATE) -> th.Tensor:
+    """griffin_lim: rounds of Griffin-Lim phase refinement from the decoded phase (0: none, the reference's single inversion);
+    loudness: the integrated loudness in LUFS to bring the waveform to, under the true-peak ceiling peak_dbtp (None: the level the
+    codec gives, as the reference), measured at `sample_rate`"""
     _check_magn_phase(magn_phase)
+    if loudness is not None:
+        loud_ops.check_targets(loudness, peak_dbtp)
     if griffin_lim:
-        return _griffin_lim(magn_phase, n_iter=griffin_lim, momentum=momentum)
-    dev = magn_phase.device if magn_phase.is_cuda else _device()
-    mp = magn_phase.to(dev, th.float32).contiguous()
-    return ops.codec_inv(mp, _bark_vector(constant.N_FFT // 2, dev))
+        wav = _griffin_lim(magn_phase, n_iter=griffin_lim, momentum=momentum)
+    else:
+        dev = magn_phase.device if magn_phase.is_cuda else _device()
+        mp = magn_phase.to(dev, th.float32).contiguous()
+        wav = ops.codec_inv(mp, _bark_vector(constant.N_FFT // 2, dev))
+    return wav if loudness is None else normalize_loudness(wav, sample_rate, loudness, peak_dbtp)
 
 
-def magn_phase_to_wav(magn_phase: th.Tensor, wav_path: str, sample_rate: int, griffin_lim: int = 0, momentum: float = 0.99):
-    raw_audio = magn_phase_to_waveform(magn_phase, griffin_lim=griffin_lim, momentum=momentum)
+def magn_phase_to_wav(magn_phase: th.Tensor, wav_path: str, sample_rate: int, griffin_lim: int = 0, momentum: float = 0.99,
+                      loudness=None, peak_dbtp: float = -1.0):
+    """loudness / peak_dbtp: as `magn_phase_to_waveform`; the file is normalised after Griffin-Lim and before the writer"""
+    extra = {} if loudness is None else {"loudness": loudness, "peak_dbtp": peak_dbtp, "sample_rate": sample_rate}
+    raw_audio = magn_phase_to_waveform(magn_phase, griffin_lim=griffin_lim, momentum=momentum, **extra)
     wavio.save(wav_path, raw_audio[None, :], sample_rate)

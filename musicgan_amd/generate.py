@@ -20,9 +20,14 @@ def _load_generator(rand_channels: int, checkpoint: str, device: torch.device) -
 
 
 def generate(output_dir: str, rand_channels: int, gen_dict_state: str, nb_vec: int, nb_music: int,
-             audio_format: str = "wav", griffin_lim: int = 0) -> None:
+             audio_format: str = "wav", griffin_lim: int = 0, loudness=None, peak_dbtp: float = -1.0) -> None:
     """audio_format: "wav" (32-bit float, the reference's output), "flac" (24-bit) or "ogg" (Ogg Vorbis at the default quality),
-    the last two encoded on the GPU; griffin_lim: rounds of Griffin-Lim phase refinement before the file is written (0: none)"""
+    the last two encoded on the GPU; griffin_lim: rounds of Griffin-Lim phase refinement before the file is written (0: none);
+    loudness: bring every file to this integrated loudness in LUFS (ITU-R BS.1770-4) under the true-peak ceiling peak_dbtp in dBTP
+    (None: the level the codec gives)"""
+    if loudness is not None:
+        from . import loud_ops
+        loud_ops.check_targets(loudness, peak_dbtp)
     if isinstance(griffin_lim, bool) or not isinstance(griffin_lim, int) or griffin_lim < 0:
         raise ValueError(f"griffin_lim must be a non-negative integer, got {griffin_lim!r}")
     if audio_format not in ("wav", "flac", "ogg"):
@@ -43,4 +48,5 @@ def generate(output_dir: str, rand_channels: int, gen_dict_state: str, nb_vec: i
         for idx, z in enumerate(latents.split(1, dim=0)):
             image = gen(z.contiguous(), 1.0)
             audio.magn_phase_to_wav(image, os.path.join(output_dir, f"sound_{idx}.{audio_format}"), audio.SAMPLE_RATE,
-                                    **({"griffin_lim": griffin_lim} if griffin_lim else {}))
+                                    **({"griffin_lim": griffin_lim} if griffin_lim else {}),
+                                    **({"loudness": loudness, "peak_dbtp": peak_dbtp} if loudness is not None else {}))
