@@ -10,6 +10,7 @@ import torch
 
 from . import _lib
 from ._lib import AdamTensorDevEma, check
+from .ops import _chk_typed, _s
 
 
 def ema_weight(decay: float) -> float:
@@ -17,14 +18,6 @@ def ema_weight(decay: float) -> float:
     if not 0.0 <= decay < 1.0:
         raise ValueError(f"0 <= decay < 1 expected, got {decay!r}")
     return ctypes.c_float(1.0 - float(decay)).value
-
-
-def _chk_adam(what: str, ts: Sequence[torch.Tensor], dtype=torch.float32):
-    for t in ts:
-        if not t.is_cuda:
-            raise _lib.MusicGanHipError(f"{what}: tensors on a ROCm GPU expected (no CPU fallback)")
-        if t.dtype != dtype or not t.is_contiguous():
-            raise _lib.MusicGanHipError(f"{what}: contiguous {dtype} expected, got {t.dtype} contiguous={t.is_contiguous()}")
 
 
 def adam_step_ema(params: Sequence[torch.Tensor], grads: Sequence[torch.Tensor], exp_avg: Sequence[torch.Tensor],
@@ -38,8 +31,8 @@ def adam_step_ema(params: Sequence[torch.Tensor], grads: Sequence[torch.Tensor],
     if len(params) < 1 or any(len(x) != len(params) for x in lists):
         raise ValueError(f"six non-empty lists of one length expected, got lengths {[len(x) for x in lists]}")
     for x in (params, grads, exp_avg, exp_avg_sq, ema):
-        _chk_adam("adam_step_ema", x)
-    _chk_adam("adam_step_ema", steps, dtype=torch.int32)
+        _chk_typed("adam_step_ema", *x)
+    _chk_typed("adam_step_ema", *steps, dtype=torch.int32)
     for i, p in enumerate(params):
         if any(x[i].numel() != p.numel() for x in (grads, exp_avg, exp_avg_sq, ema)) or steps[i].numel() != 1:
             raise ValueError(f"adam_step_ema: tensor {i}: {p.numel()} elements expected in grad, moments and average, one in the step")
@@ -50,6 +43,5 @@ def adam_step_ema(params: Sequence[torch.Tensor], grads: Sequence[torch.Tensor],
         AdamTensorDevEma(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), s.data_ptr(), e.data_ptr())
         for p, g, m, v, s, e in zip(*lists)])   # host records; the library hands them to the kernel by value
     with torch.cuda.device(params[0].device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         check(_lib.load().mg_adam_step_dev_ema(ctypes.cast(recs, ctypes.c_void_p), len(params), lr, beta1, beta2, eps,
-                                               float(grad_scale), weight, stream), "mg_adam_step_dev_ema")
+                                               float(grad_scale), weight, _s()), "mg_adam_step_dev_ema")

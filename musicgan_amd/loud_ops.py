@@ -1,8 +1,8 @@
 """Tensor-level wrappers over the loudness entries of the C ABI (include/musicgan_hip.h, csrc/loudness.hip): K-weighted segment
 energies, the BS.1770 gates, true peak, and the gain that brings a waveform to a target.  Waveforms are float32 (C, L) with C <= 8
 and unit stride along L (any row stride).  Every call is asynchronous on the caller's current stream and synchronises nothing: the
-measurements stay in device memory, and so does the gain between measurement and scaling.  Scratch memory comes from `workspace`
-(one buffer per device and stream, grown geometrically).  No fallback path exists: non-GPU tensors raise."""
+measurements stay in device memory, and so does the gain between measurement and scaling.  Scratch memory comes from `ops.workspace`
+(one buffer per device and stream, shared with the other op modules).  No fallback path exists: non-GPU tensors raise."""
 from __future__ import annotations
 
 import ctypes
@@ -12,18 +12,10 @@ import torch
 
 from . import _lib, ops
 from ._lib import check
+from .ops import _p, _s
 
 CHUNK = 1024                  # samples per chunk of the carried filter state (CHUNK of csrc/loudness.hip, mg_loudness_chunk)
 MAX_CHANNELS = 8
-_ws_cache = {}
-
-
-def _p(t: torch.Tensor):
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def _s():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def check_sample_rate(sample_rate) -> int:
@@ -87,16 +79,6 @@ def _chk(name: str, x: torch.Tensor) -> None:
         raise _lib.MusicGanHipError(f"{name}: float32 (C, L) with unit stride along L expected, got {x.dtype} strides {x.stride()}")
 
 
-def workspace(nbytes: int, device) -> torch.Tensor:
-    """Scratch buffer per (device, stream); grown geometrically, reused across calls on that stream."""
-    key = (device.index, torch.cuda.current_stream().cuda_stream)
-    buf = _ws_cache.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(nbytes, 1 << 20, 0 if buf is None else 2 * buf.numel()), dtype=torch.uint8, device=device)
-        _ws_cache[key] = buf
-    return buf
-
-
 def segment_energies(x: torch.Tensor, sample_rate: int) -> torch.Tensor:
     """x float32 (C, L) -> S float64 (C, L // seg): the sum of squares of the K-weighted channel over every whole 100 ms segment
     (seg = segment_length(sample_rate)); the filter starts from zero state at sample 0, state and sums are float64, the tail is
@@ -113,7 +95,7 @@ def segment_energies(x: torch.Tensor, sample_rate: int) -> torch.Tensor:
     nbytes = int(lib.mg_loudness_ws_bytes(channels, length, seg))
     if nbytes == 0:
         raise ValueError(f"segment_energies: {length} samples are too many")
-    ws = workspace(nbytes, x.device)
+    ws = ops.workspace(nbytes, x.device)
     check(lib.mg_loudness_energy(_p(x), channels, length, x.stride(0), seg, coef, _p(out), _p(ws), nbytes, _s()), "mg_loudness_energy")
     return out
 
@@ -145,7 +127,7 @@ def true_peak(x: torch.Tensor) -> torch.Tensor:
     lib = _lib.load()
     bank = ops.resample_bank(1, 4, 6, 0.99, x.device)
     nbytes = int(lib.mg_true_peak_ws_bytes(channels, length))
-    ws = workspace(nbytes, x.device)
+    ws = ops.workspace(nbytes, x.device)
     out = torch.empty((1,), dtype=torch.float32, device=x.device)
     check(lib.mg_true_peak(_p(x), channels, length, x.stride(0), _p(bank), bank.numel(), _p(out), _p(ws), nbytes, _s()), "mg_true_peak")
     return out[0]

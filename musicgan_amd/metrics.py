@@ -71,7 +71,7 @@ def laplacian_pyramid(x: torch.Tensor, levels: int) -> List[torch.Tensor]:
         out.append(ops.swd_pyr_lap(g, nxt))
         g = nxt
     if levels == 1:
-        ops._chk_swd("laplacian_pyramid", x)
+        ops._chk_typed("laplacian_pyramid", x)
     out.append(g)
     return out
 
@@ -92,7 +92,7 @@ def patch_descriptors(level: torch.Tensor, centres: torch.Tensor, out: Optional[
     if out is None:
         if row:
             raise ValueError("a row offset needs the buffers to append to")
-        ops._chk_swd("patch_descriptors", level)
+        ops._chk_typed("patch_descriptors", level)
         out = (torch.empty((n * p, c * patch * patch), dtype=torch.float32, device=level.device),
                torch.empty((n, c, 2), dtype=torch.float64, device=level.device))
     desc, stats = out
@@ -134,7 +134,7 @@ def sliced_wasserstein(desc_a: torch.Tensor, stats_a: torch.Tensor, desc_b: torc
                          f"{tuple(stats_b.shape)}")
     d = directions.shape[0]
     per_image = (m // stats_a.shape[0]) * patch * patch
-    ops._chk_swd("sliced_wasserstein", desc_a, desc_b, directions)
+    ops._chk_typed("sliced_wasserstein", desc_a, desc_b, directions)
     if work is None:
         work = torch.empty((2, d, m), dtype=torch.float32, device=desc_a.device)
     if out is None:
@@ -201,7 +201,7 @@ class SWD:
         n, done = batch.shape[0], self._count[which]
         if done + n > self.images:
             raise ValueError(f"{done + n} images fed, the evaluation was sized for {self.images}")
-        ops._chk_swd("SWD.feed", batch)
+        ops._chk_typed("SWD.feed", batch)
         if self._dev is None:
             self._setup(batch.device)
         for i, lvl in enumerate(laplacian_pyramid(batch, len(self.sides))):
@@ -257,7 +257,7 @@ def ms_ssim_terms(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """(n, S) float64: per pair the mean of cs over channels and valid pixels of the scales 0 .. S-2, then the mean of ssim of
     the last scale -- the factors of ms_ssim before the clamp and the weights"""
     scales = _check_pairs(a, b)
-    ssim_ops._chk_ssim("ms_ssim_terms", a, b)
+    ops._chk_typed("ms_ssim_terms", a, b)
     values = torch.empty(a.shape[0], dtype=torch.float64, device=a.device)
     terms = torch.empty((a.shape[0], scales), dtype=torch.float64, device=a.device)
     ssim_ops.ms_ssim_into(a, b, values, terms)
@@ -268,7 +268,7 @@ def ms_ssim(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """(n,) float64 cuda: MS-SSIM of every pair (a[i], b[i]) of two float32 cuda batches (n, C, H, W) with values in [-1, 1]; a
     pair's value depends on its own pixels alone.  A negative mean at any scale makes the pair's value exactly 0."""
     _check_pairs(a, b)
-    ssim_ops._chk_ssim("ms_ssim", a, b)
+    ops._chk_typed("ms_ssim", a, b)
     values = torch.empty(a.shape[0], dtype=torch.float64, device=a.device)
     ssim_ops.ms_ssim_into(a, b, values)
     return values
@@ -293,7 +293,7 @@ class MSSSIM:
         n = a.shape[0]
         if self._count + n > self.pairs:
             raise ValueError(f"{self._count + n} pairs fed, the evaluation was sized for {self.pairs}")
-        ssim_ops._chk_ssim("MSSSIM.feed", a, b)
+        ops._chk_typed("MSSSIM.feed", a, b)
         if self._values is None:
             self._values = torch.empty(self.pairs, dtype=torch.float64, device=a.device)
         ssim_ops.ms_ssim_into(a, b, self._values, None, self._count)
@@ -321,7 +321,7 @@ def _rows(x: torch.Tensor, what: str) -> torch.Tensor:
     """(N, ...) -> (N, D), a view; N >= 1 and D >= 1"""
     if x.dim() < 2 or x.shape[0] < 1 or x[0].numel() < 1:
         raise ValueError(f"{what}: a non-empty batch (N, ...) expected, got {tuple(x.shape)}")
-    nn_ops._chk_nn(what, x)
+    ops._chk_typed(what, x)
     return x.view(x.shape[0], -1)
 
 

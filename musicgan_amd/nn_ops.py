@@ -4,32 +4,16 @@ scratch memory (the per-chunk partial sums) is allocated here with torch.empty, 
 tensors raise."""
 from __future__ import annotations
 
-import ctypes
 from typing import Optional
 
 import torch
 
 from . import _lib
 from ._lib import check
+from .ops import _chk_typed, _p, _s
 
 MAX_K = 16
 EMPTY = torch.finfo(torch.float64).max   # the distance of a slot of a best list that holds no neighbour yet (its id is -1)
-
-
-def _p(t: Optional[torch.Tensor]):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _s():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _chk_nn(what: str, *ts, dtype=torch.float32):
-    for t in ts:
-        if not t.is_cuda:
-            raise _lib.MusicGanHipError(f"{what}: tensors on a ROCm GPU expected (no CPU fallback)")
-        if t.dtype != dtype or not t.is_contiguous():
-            raise _lib.MusicGanHipError(f"{what}: contiguous {dtype} expected, got {t.dtype} contiguous={t.is_contiguous()}")
 
 
 def nn_chunk() -> int:
@@ -44,12 +28,12 @@ def nn_ws_bytes(nq: int, nr: int, d: int) -> int:
 
 def nn_sqnorm(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x (n, D) float32 -> all of out (n,) float64: every row's sum of squares, added in an order that depends on D alone"""
-    _chk_nn("nn_sqnorm", x)
+    _chk_typed("nn_sqnorm", x)
     if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
         raise ValueError(f"a non-empty (n, D) matrix expected, got {tuple(x.shape)}")
     if out is None:
         out = torch.empty(x.shape[0], dtype=torch.float64, device=x.device)
-    _chk_nn("nn_sqnorm", out, dtype=torch.float64)
+    _chk_typed("nn_sqnorm", out, dtype=torch.float64)
     assert tuple(out.shape) == (x.shape[0],)
     check(_lib.load().mg_nn_sqnorm(_p(x), x.shape[0], x.shape[1], _p(out), _s()), "mg_nn_sqnorm")
     return out
@@ -58,15 +42,15 @@ def nn_sqnorm(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tens
 def nn_sqdist(q: torch.Tensor, r: torch.Tensor, qn: torch.Tensor, rn: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """q (nq, D), r (nr, D) float32 and their nn_sqnorm qn (nq,), rn (nr,) -> all of out (nq, nr) float64: max(0, qn + rn - 2 q.r).
     A pair's value depends on its two rows alone."""
-    _chk_nn("nn_sqdist", q, r)
-    _chk_nn("nn_sqdist", qn, rn, dtype=torch.float64)
+    _chk_typed("nn_sqdist", q, r)
+    _chk_typed("nn_sqdist", qn, rn, dtype=torch.float64)
     if q.dim() != 2 or r.dim() != 2 or q.shape[1] != r.shape[1] or min(q.shape[0], r.shape[0], q.shape[1]) < 1:
         raise ValueError(f"two non-empty matrices (nq, D) and (nr, D) expected, got {tuple(q.shape)} and {tuple(r.shape)}")
     nq, nr, d = q.shape[0], r.shape[0], q.shape[1]
     assert tuple(qn.shape) == (nq,) and tuple(rn.shape) == (nr,)
     if out is None:
         out = torch.empty((nq, nr), dtype=torch.float64, device=q.device)
-    _chk_nn("nn_sqdist", out, dtype=torch.float64)
+    _chk_typed("nn_sqdist", out, dtype=torch.float64)
     assert tuple(out.shape) == (nq, nr)
     nbytes = nn_ws_bytes(nq, nr, d)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
@@ -79,10 +63,10 @@ def nn_merge(dist: torch.Tensor, rid: torch.Tensor, best_d: torch.Tensor, best_i
     """the candidates dist (nq, nr) float64 with the ids rid (nr,) int64 into the best lists best_d (nq, k) float64 and best_i
     (nq, k) int64, both rewritten whole: ascending by (distance, id), an empty slot is (EMPTY, -1).  A candidate whose id equals
     qid[i] >= 0 (int64, optional) is not a neighbour of query i."""
-    _chk_nn("nn_merge", dist, best_d, dtype=torch.float64)
-    _chk_nn("nn_merge", rid, best_i, dtype=torch.int64)
+    _chk_typed("nn_merge", dist, best_d, dtype=torch.float64)
+    _chk_typed("nn_merge", rid, best_i, dtype=torch.int64)
     if qid is not None:
-        _chk_nn("nn_merge", qid, dtype=torch.int64)
+        _chk_typed("nn_merge", qid, dtype=torch.int64)
     if dist.dim() != 2 or best_d.dim() != 2 or dist.shape[0] < 1 or dist.shape[1] < 1:
         raise ValueError(f"dist (nq, nr) and best lists (nq, k) expected, got {tuple(dist.shape)} and {tuple(best_d.shape)}")
     nq, nr = dist.shape

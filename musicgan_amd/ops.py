@@ -33,11 +33,21 @@ def _chk(*ts):
             raise _lib.MusicGanHipError(f"expected contiguous float32, got {t.dtype} contiguous={t.is_contiguous()}")
 
 
+def _chk_typed(what: str, *ts, dtype=torch.float32):
+    for t in ts:
+        if not t.is_cuda:
+            raise _lib.MusicGanHipError(f"{what}: tensors on a ROCm GPU expected (no CPU fallback)")
+        if t.dtype != dtype or not t.is_contiguous():
+            raise _lib.MusicGanHipError(f"{what}: contiguous {dtype} expected, got {t.dtype} contiguous={t.is_contiguous()}")
+
+
 _ws_cache = {}
 
 
 def workspace(nbytes: int, device) -> torch.Tensor:
-    """Scratch buffer per (device, stream); grown geometrically, reused across calls on that stream."""
+    """Scratch buffer per (device, stream), shared by every op module; grown geometrically, reused across calls on that stream.
+    A caller passes it to one library call on that stream and is done with it: it is never held across another wrapper that asks
+    for a workspace."""
     key = (device.index, torch.cuda.current_stream().cuda_stream)
     buf = _ws_cache.get(key)
     if buf is None or buf.numel() < nbytes:
@@ -47,11 +57,23 @@ def workspace(nbytes: int, device) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------ conv 3x3
+def _call_channels(co: int, ci: int, dgrad: bool):
+    """(cin, cout) as the kernel sees a weight [co][ci][3][3]: a data-gradient pack runs the conv from co to ci channels"""
+    return (co, ci) if dgrad else (ci, co)
+
+
+def _conv_outputs(n: int, cout: int, h: int, w: int, want_y: bool, pixnorm: bool, device, out=None):
+    """(y, p, rn) of a conv: y (`out` if given; None with pixnorm unless want_y), and with pixnorm the normalised p and its 1/norm rn"""
+    new = lambda c: torch.empty((n, c, h, w), dtype=torch.float32, device=device)
+    y = out if out is not None else (new(cout) if (want_y or not pixnorm) else None)
+    return (y, new(cout), new(1)) if pixnorm else (y, None, None)
+
+
 def pack_conv3x3(w: torch.Tensor, dgrad: bool) -> torch.Tensor:
     _chk(w)
     co, ci = w.shape[0], w.shape[1]
     lib = _lib.load()
-    cin_call, cout_call = (co, ci) if dgrad else (ci, co)
+    cin_call, cout_call = _call_channels(co, ci, dgrad)
     wp = torch.empty(lib.mg_conv3x3_packed_floats(cin_call, cout_call), dtype=torch.float32, device=w.device)
     check(lib.mg_conv3x3_pack(_p(w), _p(wp), co, ci, int(dgrad), _s()), "mg_conv3x3_pack")
     return wp
@@ -62,7 +84,7 @@ def pack_wino3x3(w: torch.Tensor, dgrad: bool) -> torch.Tensor:
     _chk(w)
     co, ci = w.shape[0], w.shape[1]
     lib = _lib.load()
-    cin_call, cout_call = (co, ci) if dgrad else (ci, co)
+    cin_call, cout_call = _call_channels(co, ci, dgrad)
     up = torch.empty(lib.mg_wino3x3_packed_floats(cin_call, cout_call), dtype=torch.float32, device=w.device)
     check(lib.mg_wino3x3_pack(_p(w), _p(up), co, ci, int(dgrad), _s()), "mg_wino3x3_pack")
     return up
@@ -71,7 +93,7 @@ def pack_wino3x3(w: torch.Tensor, dgrad: bool) -> torch.Tensor:
 def packed_floats(kind: int, co: int, ci: int, dgrad: bool) -> int:
     """Size of the packed layout `kind` (_lib.MG_PACK_*) of a weight [co][ci][3][3]."""
     lib = _lib.load()
-    cin_call, cout_call = (co, ci) if dgrad else (ci, co)
+    cin_call, cout_call = _call_channels(co, ci, dgrad)
     if kind == _lib.MG_PACK_CONV3X3:
         return lib.mg_conv3x3_packed_floats(cin_call, cout_call)
     if kind == _lib.MG_PACK_WINO3X3:
@@ -148,12 +170,7 @@ def conv3x3(x, wp, bias, cout: int, *, ups=False, lrelu=False, mask_aux=None, pi
     flags = (MG_CONV_UPS_IN if ups else 0) | (MG_CONV_LRELU if lrelu else 0) | \
             (MG_CONV_MASK_AUX if mask_aux is not None else 0) | (MG_CONV_PIXNORM if pixnorm else 0) | \
             (MG_CONV_POOL_OUT if pool else 0)
-    y = out if out is not None else (
-        torch.empty((n, cout, h, w), dtype=torch.float32, device=x.device) if (want_y or not pixnorm) else None)
-    p = rn = None
-    if pixnorm:
-        p = torch.empty((n, cout, h, w), dtype=torch.float32, device=x.device)
-        rn = torch.empty((n, 1, h, w), dtype=torch.float32, device=x.device)
+    y, p, rn = _conv_outputs(n, cout, h, w, want_y, pixnorm, x.device, out)
     if pool:
         p = pool_out if pool_out is not None else torch.empty((n, cout, h // 2, w // 2), dtype=torch.float32,
                                                               device=x.device)
@@ -253,11 +270,7 @@ def upconv3x3(x, wp, bias, cout: int, *, lrelu=False, pixnorm=False, want_y=True
     n, cin, hin, win = x.shape
     h, w = 2 * hin, 2 * win
     flags = (MG_CONV_LRELU if lrelu else 0) | (MG_CONV_PIXNORM if pixnorm else 0)
-    y = torch.empty((n, cout, h, w), dtype=torch.float32, device=x.device) if (want_y or not pixnorm) else None
-    p = rn = None
-    if pixnorm:
-        p = torch.empty((n, cout, h, w), dtype=torch.float32, device=x.device)
-        rn = torch.empty((n, 1, h, w), dtype=torch.float32, device=x.device)
+    y, p, rn = _conv_outputs(n, cout, h, w, want_y, pixnorm, x.device)
     check(_lib.load().mg_upconv3x3(_p(x), _p(wp), _p(bias), _p(y), _p(p), _p(rn), n, cin, cout, hin, win, flags, SLOPE, _s()),
           "mg_upconv3x3")
     return (y, p, rn) if pixnorm else y
@@ -290,11 +303,7 @@ def winoups3x3(x, up, bias, cout: int, *, lrelu=False, pixnorm=False, want_y=Tru
     n, cin, hin, win = x.shape
     h, w = 2 * hin, 2 * win
     flags = (MG_CONV_LRELU if lrelu else 0) | (MG_CONV_PIXNORM if pixnorm else 0)
-    y = torch.empty((n, cout, h, w), dtype=torch.float32, device=x.device) if (want_y or not pixnorm) else None
-    p = rn = None
-    if pixnorm:
-        p = torch.empty((n, cout, h, w), dtype=torch.float32, device=x.device)
-        rn = torch.empty((n, 1, h, w), dtype=torch.float32, device=x.device)
+    y, p, rn = _conv_outputs(n, cout, h, w, want_y, pixnorm, x.device)
     check(_lib.load().mg_winoups3x3(_p(x), _p(up), _p(bias), _p(y), _p(p), _p(rn), n, cin, cout, hin, win, flags, SLOPE, _s()), "mg_winoups3x3")
     return (y, p, rn) if pixnorm else y
 
@@ -1539,17 +1548,9 @@ def vorbis_encode(wav: torch.Tensor, sample_rate: int, quality=3.0, name: str = 
 
 
 # ------------------------------------------------------------------ sliced Wasserstein distance (musicgan_amd/metrics.py)
-def _chk_swd(what: str, *ts, dtype=torch.float32):
-    for t in ts:
-        if not t.is_cuda:
-            raise _lib.MusicGanHipError(f"{what}: tensors on a ROCm GPU expected (no CPU fallback)")
-        if t.dtype != dtype or not t.is_contiguous():
-            raise _lib.MusicGanHipError(f"{what}: contiguous {dtype} expected, got {t.dtype} contiguous={t.is_contiguous()}")
-
-
 def swd_pyr_down(x: torch.Tensor) -> torch.Tensor:
     """(N, C, H, W) -> (N, C, H/2, W/2): the 5 x 5 binomial filter with mirrored borders, sampled at even rows and columns"""
-    _chk_swd("swd_pyr_down", x)
+    _chk_typed("swd_pyr_down", x)
     n, c, h, w = x.shape
     out = torch.empty((n, c, h // 2, w // 2), dtype=torch.float32, device=x.device)
     check(_lib.load().mg_swd_pyr_down(_p(x), _p(out), n * c, h, w, _s()), "mg_swd_pyr_down")
@@ -1558,7 +1559,7 @@ def swd_pyr_down(x: torch.Tensor) -> torch.Tensor:
 
 def swd_pyr_lap(x: torch.Tensor, coarse: torch.Tensor) -> torch.Tensor:
     """x - up(coarse) for x (N, C, H, W) and coarse (N, C, H/2, W/2)"""
-    _chk_swd("swd_pyr_lap", x, coarse)
+    _chk_typed("swd_pyr_lap", x, coarse)
     n, c, h, w = x.shape
     assert coarse.shape == (n, c, h // 2, w // 2)
     out = torch.empty_like(x)
@@ -1569,9 +1570,9 @@ def swd_pyr_lap(x: torch.Tensor, coarse: torch.Tensor) -> torch.Tensor:
 def swd_gather(level: torch.Tensor, centres: torch.Tensor, desc: torch.Tensor, stats: torch.Tensor, patch: int, row: int) -> None:
     """level (N, C, H, W), centres (N, P, 2) int32 -> rows row .. row + N P of desc (M, C patch^2) and the per-image float64
     (sum, sum of squares) pairs stats[row / P + n, c]"""
-    _chk_swd("swd_gather", level, desc)
-    _chk_swd("swd_gather", centres, dtype=torch.int32)
-    _chk_swd("swd_gather", stats, dtype=torch.float64)
+    _chk_typed("swd_gather", level, desc)
+    _chk_typed("swd_gather", centres, dtype=torch.int32)
+    _chk_typed("swd_gather", stats, dtype=torch.float64)
     n, c, h, w = level.shape
     p = centres.shape[1]
     check(_lib.load().mg_swd_gather(_p(level), _p(centres), _p(desc), _p(stats), n, c, h, w, p, patch, row, desc.shape[0], _s()),
@@ -1580,7 +1581,7 @@ def swd_gather(level: torch.Tensor, centres: torch.Tensor, desc: torch.Tensor, s
 
 def swd_stats_finish(stats: torch.Tensor, per_image: int) -> torch.Tensor:
     """(images, C, 2) float64 sums -> (C, 3) float32: mean, 1 / std, std (population) over images * per_image values per channel"""
-    _chk_swd("swd_stats_finish", stats, dtype=torch.float64)
+    _chk_typed("swd_stats_finish", stats, dtype=torch.float64)
     images, c, _ = stats.shape
     norm = torch.empty((c, 3), dtype=torch.float32, device=stats.device)
     check(_lib.load().mg_swd_stats_finish(_p(stats), _p(norm), images, c, per_image, _s()), "mg_swd_stats_finish")
@@ -1589,7 +1590,7 @@ def swd_stats_finish(stats: torch.Tensor, per_image: int) -> torch.Tensor:
 
 def swd_project(desc: torch.Tensor, norm: torch.Tensor, dirs: torch.Tensor, out: torch.Tensor, patch: int) -> torch.Tensor:
     """out (D, M) = dirs (D, K) times the normalised descriptors (M, K) transposed"""
-    _chk_swd("swd_project", desc, norm, dirs, out)
+    _chk_typed("swd_project", desc, norm, dirs, out)
     m, k = desc.shape
     d = dirs.shape[0]
     c = norm.shape[0]
@@ -1600,7 +1601,7 @@ def swd_project(desc: torch.Tensor, norm: torch.Tensor, dirs: torch.Tensor, out:
 
 def swd_sort_segments_(x: torch.Tensor) -> torch.Tensor:
     """ascending in-place sort of every row of the contiguous (S, M) tensor x"""
-    _chk_swd("swd_sort_segments_", x)
+    _chk_typed("swd_sort_segments_", x)
     s, m = x.shape
     check(_lib.load().mg_swd_sort_segments(_p(x), s, m, _s()), "mg_swd_sort_segments")
     return x
@@ -1608,7 +1609,7 @@ def swd_sort_segments_(x: torch.Tensor) -> torch.Tensor:
 
 def swd_distance(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     """out (one float32) = mean |a - b|"""
-    _chk_swd("swd_distance", a, b, out)
+    _chk_typed("swd_distance", a, b, out)
     assert a.shape == b.shape and out.numel() == 1
     lib = _lib.load()
     ws = workspace(lib.mg_swd_distance_ws_bytes(a.numel()), a.device)

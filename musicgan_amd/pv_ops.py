@@ -1,24 +1,19 @@
 """Tensor-level wrappers over the phase-vocoder entries of the C ABI (include/musicgan_hip.h, csrc/phasevocoder.hip).  Spectra are
 complex64 (512, T), frequency-major, as `ops.stft_1024` returns them; the rate is the rational number p / q.  The call is
-asynchronous on the caller's current stream and synchronises nothing; scratch memory comes from `workspace` (one buffer per device
-and stream, grown geometrically), the result from torch.empty.  No fallback path exists: non-GPU tensors raise."""
+asynchronous on the caller's current stream and synchronises nothing; scratch memory comes from `ops.workspace` (one buffer per device
+and stream, shared with the other op modules), the result from torch.empty.  No fallback path exists: non-GPU tensors raise."""
 from __future__ import annotations
 
-import ctypes
 from fractions import Fraction
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 from ._lib import check
+from .ops import _p, _s
 
 TIME_TILE = 256                                  # output frames per workgroup (TILE of csrc/phasevocoder.hip)
 MIN_RATE, MAX_RATE = Fraction(1, 8), Fraction(8)
-_ws_cache = {}
-
-
-def _p(t: torch.Tensor):
-    return ctypes.c_void_p(t.data_ptr())
 
 
 def as_rate(rate) -> Fraction:
@@ -60,16 +55,6 @@ def phase_vocoder_len(frames: int, p: int, q: int) -> int:
     return n
 
 
-def workspace(nbytes: int, device) -> torch.Tensor:
-    """Scratch buffer per (device, stream); grown geometrically, reused across calls on that stream."""
-    key = (device.index, torch.cuda.current_stream().cuda_stream)
-    buf = _ws_cache.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(nbytes, 1 << 20, 0 if buf is None else 2 * buf.numel()), dtype=torch.uint8, device=device)
-        _ws_cache[key] = buf
-    return buf
-
-
 def phase_vocoder(X: torch.Tensor, p: int, q: int) -> torch.Tensor:
     """X complex64 (512, T), rate p / q in [1/8, 8] -> complex64 (512, ceil(T q / p)): torchaudio.functional.phase_vocoder with
     phase_advance pi k / 2 (hop 256 of 1024), magnitudes and angles in float32 as torch takes them, the phase accumulated in float64
@@ -87,8 +72,7 @@ def phase_vocoder(X: torch.Tensor, p: int, q: int) -> torch.Tensor:
     nbytes = int(lib.mg_phase_vocoder_ws_bytes(frames, p, q))
     if nbytes == 0:
         raise ValueError(f"phase_vocoder: {frames} frames at rate {p}/{q} are too many (2^31 frames and more)")
-    ws = workspace(nbytes, X.device)
+    ws = ops.workspace(nbytes, X.device)
     out = torch.empty((512, n, 2), dtype=torch.float32, device=X.device)
-    check(lib.mg_phase_vocoder(_p(X), _p(out), _p(ws), nbytes, frames, p, q, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
-          "mg_phase_vocoder")
+    check(lib.mg_phase_vocoder(_p(X), _p(out), _p(ws), nbytes, frames, p, q, _s()), "mg_phase_vocoder")
     return torch.view_as_complex(out)

@@ -11,24 +11,9 @@ import torch
 
 from . import _lib
 from ._lib import check
+from .ops import _chk_typed, _p, _s
 
 WINDOW = 11
-
-
-def _p(t: Optional[torch.Tensor]):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _s():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _chk_ssim(what: str, *ts, dtype=torch.float32):
-    for t in ts:
-        if not t.is_cuda:
-            raise _lib.MusicGanHipError(f"{what}: tensors on a ROCm GPU expected (no CPU fallback)")
-        if t.dtype != dtype or not t.is_contiguous():
-            raise _lib.MusicGanHipError(f"{what}: contiguous {dtype} expected, got {t.dtype} contiguous={t.is_contiguous()}")
 
 
 def ssim_scales(h: int, w: int) -> int:
@@ -57,13 +42,13 @@ def ssim_scale(a: torch.Tensor, b: torch.Tensor, slots: torch.Tensor, a_next: Op
                b_next: Optional[torch.Tensor] = None) -> None:
     """one scale of the pairs a, b (N, C, H, W): every tile's float64 sums of cs and ssim into all of slots (N, C, tiles, 2) and,
     where given, the 2 x 2 means of a and b into all of a_next and b_next (N, C, H/2, W/2)"""
-    _chk_ssim("ssim_scale", a, b)
-    _chk_ssim("ssim_scale", slots, dtype=torch.float64)
+    _chk_typed("ssim_scale", a, b)
+    _chk_typed("ssim_scale", slots, dtype=torch.float64)
     n, c, h, w = a.shape
     assert b.shape == a.shape and (a_next is None) == (b_next is None)
     assert tuple(slots.shape) == (n, c, ssim_tiles(h, w), 2), (tuple(slots.shape), (n, c, ssim_tiles(h, w), 2))
     if a_next is not None:
-        _chk_ssim("ssim_scale", a_next, b_next)
+        _chk_typed("ssim_scale", a_next, b_next)
         assert tuple(a_next.shape) == (n, c, h // 2, w // 2) and a_next.shape == b_next.shape
     check(_lib.load().mg_ssim_scale(_p(a), _p(b), _p(a_next), _p(b_next), _p(slots), n, c, h, w, _s()), "mg_ssim_scale")
 
@@ -72,10 +57,10 @@ def ssim_finish(slots: torch.Tensor, n: int, c: int, h: int, w: int, values: tor
                 row: int = 0) -> None:
     """slots: the float64 slots of every scale of n pairs of (c, h, w) images, one scale after the other -> values[row .. row + n]
     (float64, one MS-SSIM per pair) and, where given, terms[row .. row + n] (rows, S) float64: the means before the clamp"""
-    _chk_ssim("ssim_finish", slots, values, dtype=torch.float64)
+    _chk_typed("ssim_finish", slots, values, dtype=torch.float64)
     assert values.dim() == 1
     if terms is not None:
-        _chk_ssim("ssim_finish", terms, dtype=torch.float64)
+        _chk_typed("ssim_finish", terms, dtype=torch.float64)
         assert tuple(terms.shape) == (values.shape[0], ssim_scales(h, w))
     check(_lib.load().mg_ssim_finish(_p(slots), slots.numel(), n, c, h, w, _p(values), _p(terms), row, values.shape[0], _s()),
           "mg_ssim_finish")
@@ -83,7 +68,7 @@ def ssim_finish(slots: torch.Tensor, n: int, c: int, h: int, w: int, values: tor
 
 def ssim_mean(values: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     """out (one float64) = the mean of the float64 values, added in an order that depends on their number alone"""
-    _chk_ssim("ssim_mean", values, out, dtype=torch.float64)
+    _chk_typed("ssim_mean", values, out, dtype=torch.float64)
     assert values.dim() == 1 and out.numel() == 1
     check(_lib.load().mg_ssim_mean(_p(values), values.numel(), _p(out), _s()), "mg_ssim_mean")
     return out
@@ -92,7 +77,7 @@ def ssim_mean(values: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
 def ms_ssim_into(a: torch.Tensor, b: torch.Tensor, values: torch.Tensor, terms: Optional[torch.Tensor] = None, row: int = 0) -> None:
     """MS-SSIM of the pairs (a[i], b[i]) of two (N, C, H, W) batches into values[row .. row + N] (and terms[row .. row + N]): one
     launch per scale, each leaving the next scale's images behind, then the finish.  Kernel launches only."""
-    _chk_ssim("ms_ssim_into", a, b)
+    _chk_typed("ms_ssim_into", a, b)
     if a.dim() != 4 or a.shape != b.shape or a.shape[0] < 1 or a.shape[1] < 1:
         raise ValueError(f"two non-empty (N, C, H, W) batches of one shape expected, got {tuple(a.shape)} and {tuple(b.shape)}")
     n, c, h, w = a.shape

@@ -10,8 +10,10 @@ has written yet.
   rear one GUARD bytes plus what rounds the payload up to 512, so the payload keeps the allocator's 512-byte alignment.  Guards
   hold the byte `fill`; so does the payload of `empty` / `empty_like` (0xFF: a quiet NaN as float32 / float64, -1 as int32, 255 as
   a mask byte); `zeros` / `full` keep their value.  CPU tensors are left alone unless `guard_cpu` (the self-test), pinned ones always;
-* `ops._ws_cache` (and the caches of uploaded tables) is emptied on entry, and before every wrapped call the payload of every live workspace buffer (the cache, and
-  the buffers of every `WgradDefer` seen that holds no job waiting for its flush) is filled with `fill` again;
+* `_ws_cache` (and the caches of uploaded tables) of every one of those modules that has it is emptied on entry -- the package
+  has one, `ops._ws_cache`, which the side modules reach through `ops.workspace`, so it is watched whichever module is wrapped --
+  and before every wrapped call the payload of every live workspace buffer (those caches, and the buffers of every `WgradDefer`
+  seen that holds no job waiting for its flush) is filled with `fill` again;
 * every public function of the ops module, `WgradDefer.flush` and `SmallNet.run` are wrapped through the census' `pre` / `post`
   hooks.  Before the call each device tensor argument is copied into a guarded allocation of its own (arguments that overlap in
   memory share one, at their mutual offsets) and the op receives the copy.  After the call the harness synchronises, checks
@@ -253,9 +255,10 @@ class Poison:
     def workspaces(self):
         """(label, _Alloc) of every live workspace buffer that may be poisoned now"""
         out = []
-        for t in getattr(self.module, "_ws_cache", {}).values():
-            if getattr(t, "_poison", None) is not None:
-                out.append(("workspace", t._poison))
+        for m in self.modules:
+            for t in getattr(m, "_ws_cache", {}).values():
+                if getattr(t, "_poison", None) is not None:
+                    out.append(("workspace", t._poison))
         for d in list(self._defers):
             busy = bool(d._jobs or d._jobs_d or d._lazy)
             for t in d._bufs:
@@ -560,8 +563,9 @@ def poisoned(fill=0xFF, *, module=None, inplace=None, guard_cpu=False, digest="c
                 if v is torch:
                     mp.setattr(m, attr, proxy)
         for cache in ("_ws_cache", "_resample_banks", "_venc_tables"):   # built anew inside, so that both runs make the same calls
-            if hasattr(module, cache):
-                mp.setattr(module, cache, {})
+            for m in modules:
+                if hasattr(m, cache):
+                    mp.setattr(m, cache, {})
         with census(module, LAUNCHES_OF_CLASSES if classes is None else classes) as c:
             p.census = c
 

@@ -138,7 +138,7 @@ def test_argument_errors_are_value_errors_before_any_gpu_work():
 
 
 def test_cpu_tensors_wrong_types_and_strides_are_refused_loudly():
-    from musicgan_amd import _lib, metrics, ssim_ops
+    from musicgan_amd import _lib, metrics, ops, ssim_ops
     z = torch.zeros
     with pytest.raises(_lib.MusicGanHipError):
         metrics.ms_ssim(z(1, 2, 16, 16), z(1, 2, 16, 16))
@@ -161,13 +161,13 @@ def test_cpu_tensors_wrong_types_and_strides_are_refused_loudly():
 
         def is_contiguous(self):
             return self._c
-    ssim_ops._chk_ssim("x", Cuda(z(1)))
+    ops._chk_typed("x", Cuda(z(1)))
     with pytest.raises(_lib.MusicGanHipError):
-        ssim_ops._chk_ssim("x", Cuda(z(1, dtype=torch.float64)))
+        ops._chk_typed("x", Cuda(z(1, dtype=torch.float64)))
     with pytest.raises(_lib.MusicGanHipError):
-        ssim_ops._chk_ssim("x", Cuda(z(1), contiguous=False))
+        ops._chk_typed("x", Cuda(z(1), contiguous=False))
     with pytest.raises(_lib.MusicGanHipError):
-        ssim_ops._chk_ssim("x", Cuda(z(1)), dtype=torch.float64)
+        ops._chk_typed("x", Cuda(z(1)), dtype=torch.float64)
 
 
 def test_ops_gains_no_public_name():

@@ -89,7 +89,7 @@ def test_argument_errors_are_value_errors_before_any_gpu_work():
 
 
 def test_cpu_tensors_wrong_types_and_strides_are_refused_loudly():
-    from musicgan_amd import _lib, metrics, nn_ops
+    from musicgan_amd import _lib, metrics, nn_ops, ops
     z = torch.zeros
     f64, i64 = dict(dtype=torch.float64), dict(dtype=torch.int64)
     with pytest.raises(_lib.MusicGanHipError):
@@ -103,15 +103,15 @@ def test_cpu_tensors_wrong_types_and_strides_are_refused_loudly():
     with pytest.raises(_lib.MusicGanHipError):
         nn_ops.nn_merge(z(4, 3, **f64), z(3, **i64), z(4, 1, **f64), z(4, 1, **i64))
     # the type and layout checks themselves, on the checker the wrappers share
-    nn_ops._chk_nn("x", Cuda(z(1)))
+    ops._chk_typed("x", Cuda(z(1)))
     with pytest.raises(_lib.MusicGanHipError):
-        nn_ops._chk_nn("x", Cuda(z(1, **f64)))
+        ops._chk_typed("x", Cuda(z(1, **f64)))
     with pytest.raises(_lib.MusicGanHipError):
-        nn_ops._chk_nn("x", Cuda(z(1), contiguous=False))
+        ops._chk_typed("x", Cuda(z(1), contiguous=False))
     with pytest.raises(_lib.MusicGanHipError):
-        nn_ops._chk_nn("x", Cuda(z(1)), dtype=torch.float64)
+        ops._chk_typed("x", Cuda(z(1)), dtype=torch.float64)
     with pytest.raises(_lib.MusicGanHipError):
-        nn_ops._chk_nn("x", Cuda(z(1, **f64)), dtype=torch.int64)
+        ops._chk_typed("x", Cuda(z(1, **f64)), dtype=torch.int64)
     # shapes are checked after the device, before any launch
     with pytest.raises(ValueError):
         nn_ops.nn_sqnorm(Cuda(z(4)))

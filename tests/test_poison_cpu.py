@@ -8,6 +8,7 @@ import torch
 
 import poison
 import poison_fake_ops as fake
+import poison_fake_side as side
 from poison import PoisonError, assert_finite, compare, poisoned
 
 INPLACE = {"scale": ("out",), "add_": ("y",), "later": ("out",)}
@@ -170,6 +171,44 @@ def test_workspace_is_poisoned_again_before_every_call():
         got = fake.read_unwritten_workspace(_x())              # must not see them
     assert bool(torch.isnan(got).all())
     _fails(lambda: assert_finite(p), r"^read_unwritten_workspace: output return of call 1")
+
+
+def _side_ctx(fill):
+    return poisoned(fill, module=side, inplace={}, guard_cpu=True, classes=(), extra_modules=(fake,))
+
+
+@pytest.mark.parametrize("fill", [0x00, 0xFF])
+def test_a_workspace_borrowed_from_another_module_is_watched(fill):
+    """the wrapped module owns no cache: its scratch memory is the `_ws_cache` buffer of a module that is only patched
+    (`extra_modules`), as `pv_ops` and its siblings borrow `ops.workspace`.  That buffer is emptied on entry, filled again before every
+    wrapped call, and its guards are checked after every wrapped call."""
+    x = torch.arange(1.0, 17.0)
+    fake.workspace(64, x.device)                               # a buffer from before: must not be seen inside
+    with _side_ctx(fill) as p:
+        assert fake._ws_cache == {}
+        assert float(side.total(x)) == float(x.sum())          # leaves finite floats in the shared buffer
+        (buf,) = fake._ws_cache.values()
+        assert [label for label, _ in p.workspaces()] == ["workspace"] and p.workspaces()[0][1] is buf._poison
+        assert bool((buf[:64] != fill).any())
+        got = side.read_unwritten_workspace(x)                 # must not see them
+        assert bool((buf == fill).all()) and next(iter(fake._ws_cache.values())) is buf
+    assert bool(torch.isnan(got).all()) if fill == 0xFF else torch.equal(got, x)
+    assert len(fake._ws_cache) == 1 and not hasattr(next(iter(fake._ws_cache.values())), "_poison")   # the one from before
+    fake._ws_cache.clear()
+
+
+@pytest.mark.parametrize("reused", [False, True])
+def test_a_write_past_a_borrowed_workspace_is_reported(reused):
+    x = torch.arange(1.0, 17.0)
+
+    def run():
+        with _side_ctx(0xFF):
+            if reused:
+                side.total(x)                                  # the buffer is then older than the call that damages it
+            side.write_past_workspace(x)
+    _fails(run, r"^write_past_workspace: guard band damaged", rf"buffer workspace, bytes {_off(1024)} \.\. {_off(1027)} relative",
+           r"call: write_past_workspace x=\[16\]")
+    assert fake._ws_cache == {}
 
 
 def test_the_post_hook_changes_values_and_the_comparison_names_the_call():

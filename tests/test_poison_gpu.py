@@ -9,8 +9,8 @@ float64 comparison also judges both poisoned runs -- or a whole update of `ProGA
 (a) every line of the headline census and its two deferred sweeps; (b) the per-op parity tests over their committed shape lists;
 (c) one critic and one generator update with the real FusedAdam step at every level; (d) the audio and metric ops; (e) nothing
 left out: `REACHES` names, per group of cases, the ops it must reach (checked against the census of each case as it runs), and
-`test_every_op_has_a_poison_case` checks that every public function of `ops` and the two library calls outside it are reached or
-excluded with a reason."""
+`test_every_op_has_a_poison_case` checks that every public function of `ops` and the library calls of `optim` and `create_dataset`
+are reached or excluded with a reason; the six side modules carry their own poisoned cases (see `LIBRARY_CALLS_OUTSIDE_OPS`)."""
 import contextlib
 import importlib
 import itertools
@@ -35,8 +35,8 @@ NOT_BITWISE = ()
 
 @contextlib.contextmanager
 def library_calls():
-    """the names of the C entry points called through `_lib.check` (ops, optim, create_dataset), as a set"""
-    from musicgan_amd import _lib, ops, optim
+    """the names of the C entry points called through `_lib.check` (ops, its six side modules, optim, create_dataset), as a set"""
+    from musicgan_amd import _lib, avg_ops, gl_ops, loud_ops, nn_ops, ops, optim, pv_ops, ssim_ops
     seen = set()
     real = _lib.check
 
@@ -44,7 +44,7 @@ def library_calls():
         seen.add(what)
         return real(rc, what)
     with pytest.MonkeyPatch.context() as mp:
-        for m in (_lib, ops, optim):
+        for m in (_lib, ops, optim, ssim_ops, avg_ops, nn_ops, gl_ops, pv_ops, loud_ops):
             mp.setattr(m, "check", check)
         yield seen
 
@@ -419,7 +419,11 @@ EXCLUDED = {
     "flac_encode_args": "argument checks on the host",
     "vorbis_encode_args": "argument checks on the host",
 }
-LIBRARY_CALLS_OUTSIDE_OPS = ("mg_adam_step_dev", "mg_pt_write_samples")   # optim.py, create_dataset.py
+# the library calls made outside `ops` that the cases of this file must reach: optim.py and create_dataset.py.  The side modules
+# (ssim_ops, avg_ops, nn_ops, gl_ops, pv_ops, loud_ops) call the library too; each has its `*_on_poisoned_memory` test next to its
+# parity tests (test_msssim_gpu, test_ema_gpu, test_nn_gpu, test_griffinlim_gpu, test_phasevocoder_gpu, test_loudness_gpu), and
+# `library_calls` sees their calls wherever a case of this file reaches one.
+LIBRARY_CALLS_OUTSIDE_OPS = ("mg_adam_step_dev", "mg_pt_write_samples")
 
 
 def test_every_op_has_a_poison_case():
