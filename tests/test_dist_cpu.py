@@ -124,19 +124,34 @@ def test_own_flat_buffer_is_recognised_in_any_parameter_order():
 def test_train_sets_the_ipc_mode_itself_when_started_by_torchrun(tmp_path, monkeypatch):
     """`torchrun ... -m musicgan_amd train` never passes through bench.py's launcher: train() and create_dataset() set
     HSA_ENABLE_IPC_MODE_LEGACY=0 in their own process before the first HIP call when WORLD_SIZE > 1 (and leave a single-process
-    run's environment alone).  No GPU here: the call then fails at `cuda.set_device`, after the variable is set."""
+    run's environment alone).  Independent of whether the machine has a GPU: the first thing each does after that point --
+    `torch.cuda.set_device` in train(), the side-car glob in create_dataset() (its glob of the audio files comes before) -- raises a
+    sentinel here, so neither goes on to initialise HIP or a process group, and the call must end in exactly that sentinel."""
+    import glob
+    import types
     import pytest
     import musicgan_amd
     train_fn, create_dataset = musicgan_amd.train, musicgan_amd.create_dataset  # (the package's lazily re-exported drivers)
+
+    class ReachedFirstDeviceUse(Exception):
+        pass
+
+    def stop(*args, **kwargs):
+        raise ReachedFirstDeviceUse
+
+    audio_glob = str(tmp_path / "*.wav")
+    monkeypatch.setattr(torch.cuda, "set_device", stop)
+    monkeypatch.setattr(sys.modules[create_dataset.__module__], "glob", types.SimpleNamespace(
+        escape=glob.escape, glob=lambda pattern: [] if pattern == audio_glob else stop()))
     for fn in (lambda: train_fn("t", str(tmp_path), str(tmp_path / "out")),
-               lambda: create_dataset(str(tmp_path / "*.wav"), str(tmp_path / "ds"))):
+               lambda: create_dataset(audio_glob, str(tmp_path / "ds"))):
         monkeypatch.delenv("HSA_ENABLE_IPC_MODE_LEGACY", raising=False)
         monkeypatch.setenv("WORLD_SIZE", "1")
-        with pytest.raises(Exception):
+        with pytest.raises(ReachedFirstDeviceUse):
             fn()
         assert "HSA_ENABLE_IPC_MODE_LEGACY" not in os.environ
         monkeypatch.setenv("WORLD_SIZE", "8")
         monkeypatch.setenv("RANK", "0")
-        with pytest.raises(Exception):
+        with pytest.raises(ReachedFirstDeviceUse):
             fn()
         assert os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY") == "0"
