@@ -549,7 +549,7 @@ def test_wino_wgrad_matches_autograd(shape, monkeypatch):
                                   (2, 32, 16, 64, 32, True, 0), (3, 64, 48, 32, 32, True, 1), (1, 112, 96, 16, 32, False, 0)])
 def test_wino_wgrad_scalar_addressed_loads_equal_the_general_form(case, monkeypatch):
     """(N, Cin, Cout, H, W, ups, bias_n): on maps at least 16 wide the weight-gradient kernels address their loads per chunk instead of
-    per lane (wino_wgrad.hip, FAST); the loads fetch the same values, so every sum has the same bits as with MG_WGRAD_FAST=0."""
+    per lane (ww_body in wino_wgrad.hip and wino_wgrad_narrow.hip, FAST); the loads fetch the same values, so every sum has the same bits as with MG_WGRAD_FAST=0."""
     ops = _ops()
     monkeypatch.setenv("MG_WINO_WGRAD_MIN_PIXELS", "1")
     n, ci, co, h, w, ups, bias_n = case

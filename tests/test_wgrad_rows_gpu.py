@@ -1,4 +1,4 @@
-"""The row-staged Winograd weight-gradient kernel (wino_wgrad.hip: wino_wgrad_rows_mfma, round 6) through the C ABI: against fp64
+"""The row-staged Winograd weight-gradient kernel (wino_wgrad_rows.hip: wino_wgrad_rows_mfma, round 6) through the C ABI: against fp64
 autograd of `F.conv2d` -- the reference's `aten::convolution_backward` (weight, bias) for nn.Conv2d(3x3, padding=1),
 /root/reference/music_gan/networks/generator.py:15-40, discriminator.py:14-34 -- and against the chunk-staged kernels it replaces
 (MG_WGRAD_ROWS=0), for every block shape <CT, OT> and the edge cases of its addressing: one stage per row (W = 32: both halo pixels
@@ -127,3 +127,52 @@ def test_rows_kernel_inside_a_deferred_sweep(monkeypatch):
         out[mode] = outs
     for (gw0, gb0, x, gy), (gw1, gb1, _, _) in zip(out["0"], out["1"]):
         assert _rel(gw1, gw0) <= 2e-6 and _rel(gb1, gb0) <= 2e-6
+
+
+def test_launched_splits_are_the_planners(monkeypatch, tmp_path):
+    """What is launched is what tests/test_wgrad_plan_cpu.py checks: the critic sweep of level 3, batch 8 (tests/census_level3_batch8.txt:
+    24 images, 80-160 channels, 32x32 down to 2x2 -- its tenth layer, on 1x1 maps, never reaches the Winograd kernels) through
+    mg_wino3x3_wgrad_partial_multi with the default switches; every returned job carries the split count the planner header, compiled
+    for the CPU, predicts for this device's CU count."""
+    import ctypes
+    import os
+    import wgrad_plan_shim as shim
+    from musicgan_amd import _lib
+    from routing_census import parse
+    ops = _ops()
+    for k in [k for k in os.environ if k.startswith("MG_WGRAD_") or k.startswith("MG_WINO_WGRAD")]:
+        monkeypatch.delenv(k)
+    text = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "census_level3_batch8.txt")).read()
+    lines = text.split("[critic sweep]\n")[1].split("\n[")[0].strip().split("\n")
+    assert len(lines) == 10
+    g = torch.Generator(device=DEV).manual_seed(11)
+    lib, descs, keep, shapes = _lib.load(), [], [], []
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    for line in lines:
+        a = dict(parse(line)[1])
+        n, co, h, w = a["gy"]
+        ci = a["x"][1]
+        if h == 1 and w == 1:
+            continue
+        assert ops.wino_wgrad_supported(n, ci, co, h, w)
+        x, gy = torch.randn(a["x"], device=DEV, generator=g), torch.randn(a["gy"], device=DEV, generator=g)
+        gw, gb = torch.empty(a["gw"], device=DEV), torch.empty(a["gb"], device=DEV)
+        ws = torch.empty(lib.mg_wino3x3_wgrad_ws_bytes(n, ci, co, h, w), dtype=torch.uint8, device=DEV)
+        descs.append(_lib.WgradDesc(p(x), p(gy), p(gw), p(gb), p(ws), ws.numel(), n, ci, co, h, w, 0, 0, a["bias_n"]))
+        keep.append((x, gy, gw, gb, ws))
+        shapes.append((n, ci, co, h, w, 0))
+    assert len(descs) == 9
+    arr, jobs = (_lib.WgradDesc * 9)(*descs), (_lib.WgradJob * 9)()
+    ops.check(lib.mg_wino3x3_wgrad_partial_multi(ctypes.cast(arr, ctypes.c_void_p), 9, ops.wgrad_group_chunks(),
+                                                 ctypes.cast(jobs, ctypes.c_void_p), None), "mg_wino3x3_wgrad_partial_multi")
+    ops.check(lib.mg_wino3x3_wgrad_reduce(ctypes.cast(jobs, ctypes.c_void_p), 9, None), "mg_wino3x3_wgrad_reduce")
+    torch.cuda.synchronize()
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    cpu = shim.load(tmp_path)
+    plan = shim.plan(cpu, shapes, 9, ops.wgrad_group_chunks(), n_cu, shim.switches(cpu))
+    assert plan.broken == 0
+    assert [j.nsplit for j in jobs] == [int(v) for v in plan.nsplit], n_cu
+    assert [(j.CinP, j.CoutP) for j in jobs] == [(int(c), int(o)) for c, o in zip(plan.CinP, plan.CoutP)]
+    assert (plan.group >= 0).sum() >= 2  # the sweep does exercise a grouped launch
+    for (x, gy, gw, gb, ws) in keep:
+        assert bool(torch.isfinite(gw).all()) and bool(torch.isfinite(gb).all())
