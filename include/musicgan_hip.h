@@ -668,6 +668,14 @@ int mg_host_io_probe(const char* dir, int tid, int n, int64_t file_bytes, int64_
 size_t mg_input_transform_ws_bytes(int N, int H, int W, int S);
 int mg_input_transform(const void* x, int x_is_f64, float* out, void* ws, size_t ws_bytes, int N, int H, int W, int S, float eps,
                        mg_stream_t stream);
+/* The same transform on windows cut out of a resident array: base holds `rows` samples (2,H,W) float32; row_a, row_b, off are DEVICE
+ * int32 arrays of length N.  Sample n is, for each channel and row, columns [off[n], W) of base[row_a[n]] followed by columns
+ * [0, off[n]) of base[row_b[n]] (where off[n] == 0, row_b[n] is never read and may be -1); out (N,2,S,S) is bit for bit what
+ * mg_input_transform gives on that window laid out in memory.  Two launches, no host read: the indices may be uploaded long before.
+ * The kernels TRUST the indices (0 <= row < rows, 0 <= off < W): the caller validates them on the host.  All addressing is 64-bit. */
+size_t mg_input_transform_windows_ws_bytes(int N, int H, int W, int S);
+int mg_input_transform_windows(const float* base, int64_t rows, const int32_t* row_a, const int32_t* row_b, const int32_t* off,
+                               float* out, void* ws, size_t ws_bytes, int N, int H, int W, int S, float eps, mg_stream_t stream);
 
 /* Sliced Wasserstein distance between patches of Laplacian-pyramid levels (Karras et al., ICLR 2018): the evaluation metric of
  * musicgan_amd/metrics.py, which the reference does not have (definition: DESIGN.md).  All float32 unless said otherwise.

@@ -45,7 +45,15 @@ _MODES = {
         (("--ema-decay",), dict(dest="ema_decay", type=float, default=0.0, metavar="D",
                                 help="also keep an exponential running average of the generator's weights, decay D per generator "
                                      "update (one in five iterations; Karras et al. use 0.999), saved as gen_ema_K.pt; 0: off")),
-    ], lambda a: (a.run, a.input_dataset, a.out_path), lambda a: {"ema_decay": a.ema_decay} if a.ema_decay else {}),
+        (("--resident",), dict(action="store_true",
+                               help="upload the dataset's side-car to device memory once and gather every batch there (no per-batch "
+                                    "host copy); refused when it would take more than three quarters of the free memory")),
+        (("--random-offset",), dict(dest="random_offset", action="store_true",
+                                    help="train on 512-frame windows at a random time offset into two consecutive chunks of a track, "
+                                         "redrawn every epoch (needs a dataset written by create_dataset in one process)")),
+    ], lambda a: (a.run, a.input_dataset, a.out_path),
+        lambda a: {**({"ema_decay": a.ema_decay} if a.ema_decay else {}), **({"resident": True} if a.resident else {}),
+                   **({"random_offset": True} if a.random_offset else {})}),
     "generate": ("generate", "generate", [
         (("gen_dict_state",), dict(type=str)),
         (("rand_channels",), dict(type=int)),

@@ -153,6 +153,8 @@ SIGNATURES = {
     "mg_adam_step_dev_ema": (c_int, [_P, c_int, c_float, c_float, c_float, c_float, c_float, c_float, _P]),
     "mg_input_transform_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "mg_input_transform": (c_int, [_P, c_int, _P, _P, c_size_t, c_int, c_int, c_int, c_int, c_float, _P]),
+    "mg_input_transform_windows_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "mg_input_transform_windows": (c_int, [_P, c_int64, _P, _P, _P, _P, _P, c_size_t, c_int, c_int, c_int, c_int, c_float, _P]),
     "mg_stft_1024": (c_int, [_P, _P, _P, c_int64, _P]),
     "mg_stft_1024_pcm_ws_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "mg_stft_1024_pcm": (c_int, [_P, c_int, c_int, _P, _P, _P, c_size_t, c_int64, _P]),

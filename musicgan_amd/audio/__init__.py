@@ -7,7 +7,8 @@ and `loudness`, `true_peak`, `normalize_loudness`, `kweighting_coefficients` (IT
 from . import constant as _constant
 from . import functions as _functions
 from .constant import N_FFT, N_VEC, SAMPLE_RATE, STFT_STRIDE
-from .dataset import AudioDataset, PackedAudioDataset, PackedLoader, has_packed, write_packed
+from .dataset import (AudioDataset, PackedAudioDataset, PackedLoader, ResidentDataset, ResidentLoader, WindowBatch, has_packed,
+                      window_offsets, write_packed)
 from .transforms import ChangeRange, ChannelMinMaxNorm
 
 for _name in ("wav_to_stft", "stft_to_phase_magn", "magn_phase_to_wav", "bark_magn_scale", "stft_from_waveform",
@@ -18,4 +19,5 @@ del _name
 
 __all__ = ["wav_to_stft", "stft_to_phase_magn", "magn_phase_to_wav", "bark_magn_scale", "stft_from_waveform",
            "magn_phase_to_waveform", "stft_to_stacked_phase_magn", "resample", "istft", "griffin_lim", "phase_vocoder", "time_stretch",
-           "pitch_shift", "pitch_ratio", "loudness", "true_peak", "normalize_loudness", "kweighting_coefficients", "AudioDataset", "PackedAudioDataset", "PackedLoader", "has_packed", "write_packed", "ChannelMinMaxNorm", "ChangeRange", *_constant.__all__]
+           "pitch_shift", "pitch_ratio", "loudness", "true_peak", "normalize_loudness", "kweighting_coefficients", "AudioDataset", "PackedAudioDataset", "PackedLoader",
+           "ResidentDataset", "ResidentLoader", "WindowBatch", "window_offsets", "has_packed", "write_packed", "ChannelMinMaxNorm", "ChangeRange", *_constant.__all__]

@@ -10,6 +10,12 @@ float32 array `magn_phase_f32.bin` of shape (S, 2, 512, 512) (the stored float64
 computes in float32 -- so nothing is lost) plus `magn_phase_f32.json` (count, shape, the .pt file of every row).  A batch is then
 one gather from the page cache into a pinned buffer and one asynchronous upload, double-buffered on a background thread: no
 pickle, no worker processes, no float64 on the wire.
+
+The side-car written by a single-process `create_dataset` also records the TRACKS: which runs of samples are consecutive chunks of
+one spectrum.  Two consecutive chunks share their normalisation and are contiguous in time, so any 512-frame window that straddles
+them is as valid a sample as the chunks themselves: `successors` / `window_offsets` / `gather(..., offsets)` serve such windows from
+the host, `ResidentDataset` / `ResidentLoader` from a copy of the whole array in device memory, where a batch is three int32 index
+vectors and the gather happens inside the input transform (musicgan_amd.window_ops).
 """
 from __future__ import annotations
 
@@ -18,11 +24,14 @@ import json
 import os
 import queue
 import threading
+from dataclasses import dataclass
 from typing import Iterator, List, Optional, Sequence
 
 import numpy as np
 import torch
 from torch.utils.data import Dataset
+
+from ..streams import new_stream
 
 _PATTERN = "magn_phase_*.pt"
 PACKED_BIN, PACKED_META = "magn_phase_f32.bin", "magn_phase_f32.json"
@@ -156,6 +165,45 @@ def has_packed(dataset_path: str) -> bool:
     return sizes_ok and sorted(m.get("rows", range(len(names)))) == list(range(len(names)))
 
 
+def _index_of_name(name: str) -> int:
+    return int(name[len("magn_phase_"):-len(".pt")])
+
+
+def _tracks_of(meta) -> Optional[list]:
+    """The "tracks" of a side-car's meta data -- [first_idx, count] runs in the numbering of `magn_phase_{idx}.pt` -- when they
+    are disjoint runs that cover [0, count) exactly and the files carry exactly those numbers; None otherwise (no key: written by
+    `write_packed` or a multi-rank create_dataset; a malformed key counts as absent)."""
+    tracks, count = meta.get("tracks"), int(meta["count"])
+    if not isinstance(tracks, list) or not tracks:
+        return None
+    try:
+        runs = sorted((int(f), int(c)) for f, c in tracks)
+    except (TypeError, ValueError):
+        return None
+    at = 0
+    for first, n in runs:
+        if first != at or n < 1:
+            return None
+        at += n
+    if at != count or sorted(_index_of_name(f) for f in meta.get("files", ())) != list(range(count)):
+        return None
+    return [list(r) for r in runs]
+
+
+def window_offsets(successors, seed: int, epoch: int, width: int = _SAMPLE_SHAPE[-1]) -> np.ndarray:
+    """One time offset per DATASET INDEX for epoch `epoch` of a run seeded `seed` (int32): uniform in [0, width) where the sample has
+    a successor, 0 where it has none.  Window (i, o) is columns [o, width) of item i followed by columns [0, o) of item
+    successors[i].  The draw comes from a generator of its own, `torch.Generator().manual_seed((seed * 1000003 + epoch +
+    0x9E3779B9) mod 2^32)` (the CPU generator keeps 32 bits of a seed) -- one draw of `randint(0, width, (n,))` over all n samples
+    -- so it is a function of (seed, epoch, sample) alone: it does not depend on the rank, the world size, the position in the
+    epoch or a resume, and it takes nothing from the generator behind the epoch's permutation (ShardedShuffle seeds that one with
+    seed + epoch)."""
+    succ = np.asarray(successors)
+    g = torch.Generator().manual_seed((int(seed) * 1000003 + int(epoch) + 0x9E3779B9) % (1 << 32))
+    drawn = torch.randint(0, int(width), (succ.shape[0],), generator=g, dtype=torch.int32).numpy()
+    return np.where(succ >= 0, drawn, 0).astype(np.int32)
+
+
 class PackedAudioDataset(Dataset):
     """Same items, same order as AudioDataset, served from the memory-mapped float32 side-car (items are float32).  Item i (file
     names in the reference's plain string order) lives in row `rows[i]` of the array: create_dataset streams the rows out in the
@@ -168,6 +216,9 @@ class PackedAudioDataset(Dataset):
         self._count = int(meta["count"])
         self._rows = np.asarray(meta.get("rows", range(self._count)), dtype=np.int64)
         self._k, self._b = int(meta.get("shards", 1)), int(meta.get("block_rows", PACKED_BLOCK_ROWS))
+        self._files = tuple(meta["files"])
+        self._tracks = _tracks_of(meta)
+        self._succ: Optional[np.ndarray] = None
         self._mm = [np.memmap(os.path.join(dataset_path, shard_name(i, self._k)), dtype=np.float32, mode="r", shape=(n,) + _SAMPLE_SHAPE)
                     if n else None for i, n in enumerate(shard_rows(self._count, self._k, self._b))]
 
@@ -181,11 +232,42 @@ class PackedAudioDataset(Dataset):
     def __getitem__(self, index: int) -> torch.Tensor:
         return torch.from_numpy(np.array(self._row(index)))
 
-    def gather(self, indices: Sequence[int], out: torch.Tensor) -> torch.Tensor:
-        """out[k] = sample indices[k]; `out` is a (len(indices), 2, 512, 512) float32 host tensor (pinned for async upload)."""
+    def successors(self) -> Optional[np.ndarray]:
+        """int32 array in dataset index order (names in plain string order): succ[i] is the index of `magn_phase_{idx + 1}.pt` when
+        that file is the next chunk of the track item i (`magn_phase_{idx}.pt`) belongs to, else -1 (the last chunk of a track).  None
+        when the side-car records no tracks."""
+        if self._tracks is None:
+            return None
+        if self._succ is None:
+            index_of = {_index_of_name(f): i for i, f in enumerate(self._files)}
+            succ = np.full(self._count, -1, dtype=np.int32)
+            for first, n in self._tracks:
+                for idx in range(first, first + n - 1):
+                    succ[index_of[idx]] = index_of[idx + 1]
+            self._succ = succ
+        return self._succ
+
+    def gather(self, indices: Sequence[int], out: torch.Tensor, offsets: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """out[k] = sample indices[k]; `out` is a (len(indices), 2, 512, 512) float32 host tensor (pinned for async upload).
+        With `offsets` (one per entry of `indices`): out[k] = window (indices[k], offsets[k]), columns [o, W) of the item followed by
+        columns [0, o) of its successor -- two strided copies, the same number of bytes."""
         dst = out.numpy()
-        for k, i in enumerate(indices):
-            dst[k] = self._row(i)
+        if offsets is None:
+            for k, i in enumerate(indices):
+                dst[k] = self._row(i)
+            return out
+        succ, width = self.successors(), dst.shape[-1]
+        for k, (i, o) in enumerate(zip(indices, offsets)):
+            o = int(o)
+            if o == 0:
+                dst[k] = self._row(i)
+                continue
+            if not 0 < o < width:
+                raise ValueError(f"offset {o} of item {i} outside [0, {width})")
+            if succ is None or succ[i] < 0:
+                raise ValueError(f"item {i} has no successor in its track: only offset 0 is possible, got {o}")
+            dst[k][..., :width - o] = self._row(i)[..., o:]
+            dst[k][..., width - o:] = self._row(int(succ[i]))[..., :o]
         return out
 
 
@@ -200,12 +282,17 @@ class PackedLoader:
     out of pinned[s] is still pending: it waits on the HOST for that upload's event first (a training loop under graph replay
     has no host synchronisation of its own and runs many steps ahead of the GPU)."""
 
-    def __init__(self, dataset: PackedAudioDataset, batch_size: int, sampler, device, depth: int = 3):
+    def __init__(self, dataset: PackedAudioDataset, batch_size: int, sampler, device, depth: int = 3, random_offset: bool = False):
         self.ds, self.bs, self.sampler, self.device, self.depth = dataset, batch_size, sampler, torch.device(device), depth
+        # random_offset: every sample with a successor in its track is served as a window at window_offsets(...)[sample], drawn per
+        # epoch from (sampler.seed, sampler.epoch); needs a side-car with tracks
+        self.random_offset = random_offset
+        if random_offset and dataset.successors() is None:
+            raise ValueError("random_offset needs a side-car with tracks (written by a single-process create_dataset)")
         self._pinned = [torch.empty((batch_size,) + _SAMPLE_SHAPE, dtype=torch.float32).pin_memory() for _ in range(depth)]
         self._dev = [torch.empty((batch_size,) + _SAMPLE_SHAPE, dtype=torch.float32, device=self.device) for _ in range(depth)]
         self._uploaded: List[Optional[torch.cuda.Event]] = [None] * depth  # last upload out of pinned[s] (kept across epochs)
-        self._stream = torch.cuda.Stream(device=self.device)
+        self._stream = new_stream(self.device)
 
     def __len__(self) -> int:
         return len(self.sampler) // self.bs
@@ -213,6 +300,7 @@ class PackedLoader:
     def __iter__(self) -> Iterator[torch.Tensor]:
         idx: List[int] = list(iter(self.sampler))
         nb = len(idx) // self.bs
+        offs = window_offsets(self.ds.successors(), self.sampler.seed, self.sampler.epoch) if self.random_offset else None
         ready: "queue.Queue" = queue.Queue(maxsize=self.depth - 1)
         free: "queue.Queue" = queue.Queue()
         for s in range(self.depth):
@@ -237,7 +325,11 @@ class PackedLoader:
                         return
                     if self._uploaded[slot] is not None:
                         self._uploaded[slot].synchronize()  # HOST wait: the previous upload has read pinned[slot]
-                    self.ds.gather(idx[b * self.bs:(b + 1) * self.bs], self._pinned[slot])
+                    mine = idx[b * self.bs:(b + 1) * self.bs]
+                    if offs is None:
+                        self.ds.gather(mine, self._pinned[slot])
+                    else:
+                        self.ds.gather(mine, self._pinned[slot], offs[mine])
                     with torch.cuda.stream(self._stream):
                         self._dev[slot].copy_(self._pinned[slot], non_blocking=True)
                         ev = torch.cuda.Event()
@@ -277,3 +369,101 @@ class PackedLoader:
                 except queue.Empty:
                     break
             th.join(timeout=5)
+
+
+# ------------------------------------------------------------------------------------------------- the dataset in device memory
+RESIDENT_STAGE_SAMPLES = 32  # samples of the pinned staging buffer of the upload: create_dataset's chunk (CHUNK_SAMPLES, 64 MiB)
+RESIDENT_FRACTION = 0.75  # of the free device memory the array may take: a POLICY (room for the activations of a level-7 step),
+#                           not a measurement
+
+
+def check_resident_fits(need_bytes: int, free_bytes: int, max_fraction: float = RESIDENT_FRACTION) -> None:
+    """MemoryError (naming both numbers) when an array of need_bytes would take more than max_fraction of free_bytes."""
+    if need_bytes > max_fraction * free_bytes:
+        raise MemoryError(f"the dataset needs {need_bytes} bytes of device memory, more than {max_fraction:g} of the "
+                          f"{free_bytes} bytes that are free: train without `resident` (the packed loader streams it from the host)")
+
+
+class ResidentDataset:
+    """The whole side-car in ONE float32 (S, 2, 512, 512) device tensor `data`, row i = item i of the dataset (AudioDataset order),
+    uploaded once through one pinned staging buffer of create_dataset's chunk size by the calling thread.  `max_fraction`: see
+    RESIDENT_FRACTION.  Under data-parallel training every rank holds the whole array (any rank may draw any index)."""
+
+    def __init__(self, dataset: PackedAudioDataset, device, max_fraction: float = RESIDENT_FRACTION):
+        self.packed, self.device = dataset, torch.device(device)
+        count = len(dataset)
+        need = count * int(np.prod(_SAMPLE_SHAPE)) * 4
+        free, _ = torch.cuda.mem_get_info(self.device)
+        check_resident_fits(need, free, max_fraction)
+        self.data = torch.empty((count,) + _SAMPLE_SHAPE, dtype=torch.float32, device=self.device)
+        stage = torch.empty((RESIDENT_STAGE_SAMPLES,) + _SAMPLE_SHAPE, dtype=torch.float32).pin_memory()
+        for c0 in range(0, count, RESIDENT_STAGE_SAMPLES):
+            n = min(RESIDENT_STAGE_SAMPLES, count - c0)
+            dataset.gather(range(c0, c0 + n), stage[:n])
+            self.data[c0:c0 + n].copy_(stage[:n], non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()  # the one staging buffer is refilled next
+
+    def __len__(self) -> int:
+        return self.data.shape[0]
+
+    def successors(self) -> Optional[np.ndarray]:
+        return self.packed.successors()
+
+
+@dataclass
+class WindowBatch:
+    """A batch that has not been gathered: window k is columns [offsets[k], W) of source[rows_a[k]] followed by columns
+    [0, offsets[k]) of source[rows_b[k]] (rows_b[k] = -1 and never read where offsets[k] = 0).  `source` is the resident array, the
+    three vectors are int32 views of length B into an epoch's arrays on the same device."""
+    source: torch.Tensor
+    rows_a: torch.Tensor
+    rows_b: torch.Tensor
+    offsets: torch.Tensor
+
+    def __len__(self) -> int:
+        return self.rows_a.shape[0]
+
+    def materialise(self) -> torch.Tensor:
+        """the (B, 2, H, W) float32 tensor of the windows, by tensor expressions on the device (tests, consumers other than the
+        training loop's transform)"""
+        width = self.source.shape[-1]
+        both = torch.cat([self.source[self.rows_a.long()], self.source[self.rows_b.clamp_min(0).long()]], dim=-1)
+        cols = self.offsets.long()[:, None] + torch.arange(width, device=self.source.device)[None, :]
+        return torch.gather(both, -1, cols[:, None, None, :].expand(-1, both.shape[1], both.shape[2], -1))
+
+
+class ResidentLoader:
+    """Batches of a ResidentDataset as `WindowBatch`es, in sampler order with the tail dropped (as PackedLoader).  Per epoch: the
+    sampler's indices, their offsets (`window_offsets` of (sampler.seed, sampler.epoch) with `random_offset`, else all zero) and
+    successors are validated on the host and uploaded ONCE as three int32 vectors; a batch is a view into them.  No per-batch
+    host-to-device copy, no background thread."""
+
+    def __init__(self, resident: ResidentDataset, batch_size: int, sampler, device, random_offset: bool = False):
+        self.resident, self.bs, self.sampler, self.device = resident, batch_size, sampler, torch.device(device)
+        self.random_offset = random_offset
+        if random_offset and resident.successors() is None:
+            raise ValueError("random_offset needs a side-car with tracks (written by a single-process create_dataset)")
+
+    def __len__(self) -> int:
+        return len(self.sampler) // self.bs
+
+    def __iter__(self) -> Iterator[WindowBatch]:
+        from .. import window_ops
+        idx = np.asarray(list(iter(self.sampler)), dtype=np.int32)
+        nb = len(idx) // self.bs
+        rows_a = idx[:nb * self.bs]
+        if self.random_offset:
+            succ = self.resident.successors()
+            offs = window_offsets(succ, self.sampler.seed, self.sampler.epoch, self.resident.data.shape[-1])[rows_a]
+            rows_b = np.where(offs > 0, succ[rows_a], -1).astype(np.int32)
+        else:
+            offs, rows_b = np.zeros_like(rows_a), np.full_like(rows_a, -1)
+        window_ops.check_windows(rows_a, rows_b, offs, len(self.resident), self.resident.data.shape[-1])
+        if nb == 0:
+            return
+        # the epoch's only host-to-device copy, out of pinned memory so that the host does not wait for the queue to drain
+        host = torch.from_numpy(np.stack([rows_a, rows_b, offs])).pin_memory()
+        epoch = host.to(self.device, non_blocking=True)
+        for b in range(nb):
+            lo, hi = b * self.bs, (b + 1) * self.bs
+            yield WindowBatch(self.resident.data, epoch[0, lo:hi], epoch[1, lo:hi], epoch[2, lo:hi])

@@ -16,6 +16,8 @@ unchanged path.
 `stretch` / `pitch` add re-timed and transposed copies of every file behind its own samples (audio.phase_vocoder on the file's STFT;
 for a pitch, the mono signal resampled by P / Q first and re-timed by Q / P, which restores the duration): the remedy for a small
 corpus.  Without them nothing changes.
+A single-process run records in the side-car which samples are consecutive chunks of one spectrum ("tracks": a file's own samples
+are one, each variant another): what training with random time offsets (`train --random-offset`) cuts its windows from.
 """
 import glob
 import json
@@ -29,6 +31,7 @@ import torch as th
 
 from . import audio
 from .audio import dataset as _ds
+from .streams import new_stream
 
 CHUNK_SAMPLES = 32  # samples per pinned chunk (64 MiB of float32)
 RING_CHUNKS = 6     # pinned chunks in flight between the copy streams and the writer threads
@@ -204,7 +207,7 @@ class _Loader:
         try:
             th.cuda.set_device(self.device)
             pins = [th.empty(self.STAGE_BYTES, dtype=th.uint8).pin_memory() for _ in range(2)]
-            stream = th.cuda.Stream(device=self.device)
+            stream = new_stream(self.device)
             events = [None, None]
             tdt = {np.dtype(np.int16): th.int16, np.dtype(np.int32): th.int32, np.dtype(np.uint8): th.uint8,
                    np.dtype(np.float32): th.float32}
@@ -379,7 +382,7 @@ def create_dataset(audio_path: str, dataset_output_dir: str, *, packed: bool = T
         ring.put(_Chunk(nb_vec, ring))
     # device-to-host copies go out on two streams of their own, alternating by chunk: the loop's stream never waits for a copy
     # (it used to carry them, and the per-file `.cpu()` of the CRCs then waited for 421 MB of copies each time)
-    copy_streams = [th.cuda.Stream(device=dev) for _ in range(2)]
+    copy_streams = [new_stream(dev) for _ in range(2)]
     n_chunks = 0
     # th.save's output for a (2, 512, nb_vec) float64 tensor as a template (checked against th.save at construction; None: keep
     # calling th.save): the container's CRC-32 then comes from the GPU (mg_crc32_f64) instead of one host core per sample
@@ -392,6 +395,7 @@ def create_dataset(audio_path: str, dataset_output_dir: str, *, packed: bool = T
     writers = _Writers(n_thr, template)
     side = None
     names = []
+    tracks = []  # [first idx, count] of every spectrum written (a file's own samples; each of its variants): consecutive chunks
     if packed and world == 1:
         # written row by row by the writer threads (os.pwrite at row idx): one thread streaming 421 MB per file was the
         # slowest stage of the loop
@@ -439,6 +443,7 @@ def create_dataset(audio_path: str, dataset_output_dir: str, *, packed: bool = T
                     continue  # (a variant that is too short is left out in the same way)
                 both = audio.stft_to_stacked_phase_magn(complex_values, nb_vec=nb_vec)  # (S, 2, 512, nb_vec) float32, on the device
                 n_files += v_i == 0
+                tracks.append([idx, int(both.size()[0])])
                 crcs = None
                 if template is not None:
                     from . import ops
@@ -497,7 +502,7 @@ def create_dataset(audio_path: str, dataset_output_dir: str, *, packed: bool = T
             if not ok:
                 _remove_sidecar(dataset_output_dir)
     if side is not None:
-        _finish_sidecar(dataset_output_dir, names)
+        _finish_sidecar(dataset_output_dir, names, tracks)
     if stats is not None:
         wall = time.perf_counter() - t_start
         stats.update({"files": n_files, "samples": len(names), "wall_s": wall, "setup_s": t_setup, "drain_s": t_drain,
@@ -506,10 +511,12 @@ def create_dataset(audio_path: str, dataset_output_dir: str, *, packed: bool = T
                       "writer_busy_s": writers.busy_s, "pt_bytes": len(names) * 2 * (audio.N_FFT // 2) * nb_vec * 8})
 
 
-def _finish_sidecar(folder: str, names_in_write_order) -> None:
+def _finish_sidecar(folder: str, names_in_write_order, tracks=None) -> None:
     """The rows were streamed in write order (idx 0, 1, 2, ...); AudioDataset / the loader index samples in file-NAME order
     (plain string sort, as the reference does: magn_phase_10.pt < magn_phase_2.pt).  The meta file carries the row of every
-    sorted name, so the stream never has to be permuted on disk."""
+    sorted name, so the stream never has to be permuted on disk.  `tracks` (optional): [first_idx, count] per spectrum written, in
+    the numbering of the file names -- runs of consecutive chunks of one spectrum, which the loaders cut shifted windows from
+    (audio/dataset.py); recorded under "tracks" in the same meta file."""
     k = _ds.PACKED_SHARDS
     tmps = [join(folder, _ds.shard_name(i, k) + ".tmp") for i in range(k)]
 
@@ -535,4 +542,5 @@ def _finish_sidecar(folder: str, names_in_write_order) -> None:
         json.dump({"count": len(files), "shape": list(_ds._SAMPLE_SHAPE), "dtype": "float32", "files": files, "rows": order,
                    "shards": k, "block_rows": _ds.PACKED_BLOCK_ROWS,
                    "sizes": [os.path.getsize(join(folder, f)) for f in files],
-                   "probes": [_ds.file_probe(join(folder, f)) for f in files]}, fh)
+                   "probes": [_ds.file_probe(join(folder, f)) for f in files],
+                   **({"tracks": [[int(f), int(c)] for f, c in tracks]} if tracks is not None else {})}, fh)

@@ -13,6 +13,9 @@
 // read twice (+ 2 / IT_R of it again as halo rows, mostly out of the L2), the output is 1/16 of it at 512 -> 128.
 // (r01-r03: three launches, weights and the plane's min / max recomputed per output element, a 33 MB intermediate written and read
 // back: 0.19 ms for a batch of 64 at 2x512x512 = 1.4 TB/s.)
+// mg_input_transform_windows (itw_*): the same two launches on windows cut out of a dataset that lives in device memory -- columns
+// [off, W) of one sample followed by columns [0, off) of another, by device arrays of indices -- with the gather folded into the reads;
+// the resize pass is the same __device__ body over another source accessor, so its outputs have the bits of the plain kernel's.
 #include "mg_common.h"
 
 namespace {
@@ -117,9 +120,37 @@ __host__ __device__ inline size_t it_lds_floats(const ItGeom& g) {
   return (size_t)g.S * g.kh + 2 * (size_t)g.S + (size_t)IT_R * g.kv + 2 * IT_R + 2 + (size_t)g.rows_max * g.S;
 }
 
+// Where the resize pass takes plane nc from.  `row(y, x0)` is something indexable by the tap number b that yields the plane's
+// value at row y, column x0 + b: a pointer for a plane that lies in memory as it is, and for a window (mg_input_transform_windows)
+// a pair of pointers with the column at which the second source takes over.
 template <typename T>
-__global__ void __launch_bounds__(256) it_resize_fused(const T* __restrict__ x, const float* __restrict__ part, float* __restrict__ out,
-                                                       const ItGeom g) {
+struct ItPlainSrc {
+  const T* __restrict__ plane;
+  int W;
+  __device__ __forceinline__ const T* row(int y, int x0) const { return plane + (size_t)y * W + x0; }
+};
+
+struct ItWindowRow {
+  const float* a;  // tap k of the row is a[ia + k] for k < split ...
+  const float* b;  // ... and b[ib + k] from there on (ib + k >= 0 exactly when k >= split)
+  long long ia, ib;
+  int split;
+  __device__ __forceinline__ float operator[](int k) const { return k < split ? a[ia + k] : b[ib + k]; }
+};
+
+// columns [off, W) of plane `a` followed by columns [0, off) of plane `b`; with off == 0 no tap reaches `b`
+struct ItWindowSrc {
+  const float* a;
+  const float* b;
+  int W, off;
+  __device__ __forceinline__ ItWindowRow row(int y, int x0) const {
+    const long long r = (long long)y * W;
+    return ItWindowRow{a, b, r + off + x0, r + x0 - (W - off), W - off - x0};
+  }
+};
+
+template <typename T, typename Src>
+__device__ __forceinline__ void it_resize_body(const Src src, const float* __restrict__ part, float* __restrict__ out, const ItGeom g) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   float* hw = sm;
   int* hx = reinterpret_cast<int*>(hw + (size_t)g.S * g.kh);
@@ -163,12 +194,11 @@ __global__ void __launch_bounds__(256) it_resize_fused(const T* __restrict__ x, 
   const int nin = yhi - ylo;
 
   // horizontal pass: tl[r][j] = sum_b w[j][b] * norm(x[nc][ylo + r][xmin_j + b]),  norm(v) = (v - mn) / (mx - mn + eps) * 2 - 1
-  const T* plane = x + (size_t)nc * g.H * g.W;
   for (int e = tid; e < nin * g.S; e += 256) {
     const int r = g.lgS >= 0 ? e >> g.lgS : e / g.S;
     const int j = e - r * g.S;
     const int xmin = hx[2 * j], xs = hx[2 * j + 1];
-    const T* row = plane + (size_t)(ylo + r) * g.W + xmin;
+    const auto row = src.row(ylo + r, xmin);
     const float* w = hw + (size_t)j * g.kh;
     float acc = 0.f;
     int b = 0;
@@ -194,6 +224,116 @@ __global__ void __launch_bounds__(256) it_resize_fused(const T* __restrict__ x, 
     for (int a = 0; a < ys; ++a) acc += col[(size_t)a * g.S] * w[a];
     out[((size_t)nc * g.S + i0 + i) * g.S + j] = acc;
   }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) it_resize_fused(const T* __restrict__ x, const float* __restrict__ part, float* __restrict__ out,
+                                                       const ItGeom g) {
+  it_resize_body<T>(ItPlainSrc<T>{x + (size_t)blockIdx.x * g.H * g.W, g.W}, part, out, g);
+}
+
+// ---- windows out of a resident array (mg_input_transform_windows): sample n is columns [off[n], W) of base[row_a[n]] followed by
+// columns [0, off[n]) of base[row_b[n]], per channel and row.  The indices are device arrays and are trusted.
+__device__ __forceinline__ void mm_acc(float v, float& mn, float& mx) {
+  mn = fminf(mn, v);
+  mx = fmaxf(mx, v);
+}
+
+constexpr int WM_ROWS = 4;  // rows a wave has in flight
+constexpr int WM_VEC = 2;   // 16-byte loads per lane and row in flight (128 vectors: one 512-column row)
+
+// Partial min / max of plane nc of the window over the rows of block p (H / MMP of them), in the layout of it_minmax_part.  A wave
+// takes WM_ROWS rows at a time; a row is two runs, A[off, W) and B[0, off): each is walked with scalar loads up to 16-byte alignment,
+// 16-byte loads (WM_ROWS x WM_VEC per lane issued before the first is used) and a scalar tail.  Min and max are exact in any order.
+__global__ void __launch_bounds__(256) itw_minmax_part(const float* __restrict__ base, const int* __restrict__ row_a,
+                                                       const int* __restrict__ row_b, const int* __restrict__ offs,
+                                                       float* __restrict__ part, int H, int W) {
+  __shared__ float red[16];
+  typedef float vec_t __attribute__((ext_vector_type(4)));
+  const int nc = blockIdx.x, p = blockIdx.y, n = nc >> 1, c = nc & 1;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int off = offs[n];
+  const size_t plane = (size_t)H * W;
+  const float* pa = base + ((size_t)row_a[n] * 2 + c) * plane;
+  const float* pb = off > 0 ? base + ((size_t)row_b[n] * 2 + c) * plane : pa;
+  const int per = (H + MMP - 1) / MMP;
+  const int rlo = p * per, rhi = rlo + per < H ? rlo + per : H;
+  float mn = INFINITY, mx = -INFINITY;
+  for (int r0 = rlo + wave * WM_ROWS; r0 < rhi; r0 += 4 * WM_ROWS) {
+    const float* vp[WM_ROWS][2];  // first aligned element of the row's two runs
+    int nv[WM_ROWS][2];           // 16-byte vectors of each run
+#pragma unroll
+    for (int u = 0; u < WM_ROWS; ++u) {
+      const bool live = r0 + u < rhi;
+      const size_t ro = (size_t)(live ? r0 + u : r0) * W;
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const float* q = s == 0 ? pa + ro + off : pb + ro;
+        const int len = live ? (s == 0 ? W - off : off) : 0;
+        int head = (int)((4 - ((reinterpret_cast<size_t>(q) >> 2) & 3)) & 3);
+        head = head < len ? head : len;
+        nv[u][s] = (len - head) >> 2;
+        vp[u][s] = q + head;
+        const int tail = len - head - 4 * nv[u][s];
+        // the at most 3 + 3 scalars of this run: lanes 8 s + 0..2 the head, lanes 8 s + 4..6 the tail
+        const int k = lane - 8 * s;
+        if (k >= 0 && k < head) mm_acc(q[k], mn, mx);
+        if (k >= 4 && k - 4 < tail) mm_acc(q[head + 4 * nv[u][s] + (k - 4)], mn, mx);
+      }
+    }
+    int most = 0;
+#pragma unroll
+    for (int u = 0; u < WM_ROWS; ++u) most = most > nv[u][0] + nv[u][1] ? most : nv[u][0] + nv[u][1];
+    for (int j0 = 0; j0 < most; j0 += 64 * WM_VEC) {  // (one trip for rows of up to 512 columns)
+      vec_t q[WM_ROWS][WM_VEC];
+      bool ok[WM_ROWS][WM_VEC];
+#pragma unroll
+      for (int u = 0; u < WM_ROWS; ++u)
+#pragma unroll
+        for (int k = 0; k < WM_VEC; ++k) {
+          const int j = j0 + k * 64 + lane;  // vector j of the row: run A first, then run B
+          ok[u][k] = j < nv[u][0] + nv[u][1];
+          const float* src = j < nv[u][0] ? vp[u][0] + 4 * (size_t)j : vp[u][1] + 4 * (size_t)(j - nv[u][0]);
+          if (ok[u][k]) q[u][k] = *reinterpret_cast<const vec_t*>(src);
+        }
+#pragma unroll
+      for (int u = 0; u < WM_ROWS; ++u)
+#pragma unroll
+        for (int k = 0; k < WM_VEC; ++k)
+          if (ok[u][k]) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) mm_acc(q[u][k][e], mn, mx);
+          }
+    }
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    mn = fminf(mn, __shfl_xor(mn, d));
+    mx = fmaxf(mx, __shfl_xor(mx, d));
+  }
+  if (lane == 0) {
+    red[wave] = mn;
+    red[8 + wave] = mx;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int k = 1; k < 4; ++k) {
+      mn = fminf(mn, red[k]);
+      mx = fmaxf(mx, red[8 + k]);
+    }
+    part[((size_t)nc * MMP + p) * 2] = mn;
+    part[((size_t)nc * MMP + p) * 2 + 1] = mx;
+  }
+}
+
+__global__ void __launch_bounds__(256) itw_resize_fused(const float* __restrict__ base, const int* __restrict__ row_a,
+                                                        const int* __restrict__ row_b, const int* __restrict__ offs,
+                                                        const float* __restrict__ part, float* __restrict__ out, const ItGeom g) {
+  const int n = blockIdx.x >> 1, c = blockIdx.x & 1, off = offs[n];
+  const size_t plane = (size_t)g.H * g.W;
+  const float* pa = base + ((size_t)row_a[n] * 2 + c) * plane;
+  const float* pb = off > 0 ? base + ((size_t)row_b[n] * 2 + c) * plane : pa;
+  it_resize_body<float>(ItWindowSrc{pa, pb, g.W, off}, part, out, g);
 }
 
 bool it_geometry(int H, int W, int S, float eps, ItGeom& g) {
@@ -241,4 +381,31 @@ extern "C" int mg_input_transform(const void* x, int x_is_f64, float* out, void*
   hipStream_t s = (hipStream_t)stream;
   if (x_is_f64) return run_it(reinterpret_cast<const double*>(x), out, part, N, g, s);
   return run_it(reinterpret_cast<const float*>(x), out, part, N, g, s);
+}
+
+extern "C" size_t mg_input_transform_windows_ws_bytes(int N, int H, int W, int S) { return mg_input_transform_ws_bytes(N, H, W, S); }
+
+extern "C" int mg_input_transform_windows(const float* base, int64_t rows, const int32_t* row_a, const int32_t* row_b, const int32_t* off,
+                                          float* out, void* ws, size_t ws_bytes, int N, int H, int W, int S, float eps,
+                                          mg_stream_t stream) {
+  MG_CHECK_ARG(base && rows > 0 && row_a && row_b && off && out && ws && N > 0 && H > 0 && W > 0 && S > 0,
+               "mg_input_transform_windows: bad arguments");
+  MG_CHECK_ARG(S <= H && S <= W, "mg_input_transform_windows: only down-sampling (S=%d from %dx%d) is implemented", S, H, W);
+  MG_CHECK_ARG((reinterpret_cast<size_t>(base) & 3) == 0, "mg_input_transform_windows: base is not a float32 address");
+  if (ws_bytes < mg_input_transform_windows_ws_bytes(N, H, W, S)) {
+    mg_set_error("mg_input_transform_windows: workspace too small");
+    return MG_EWORKSPACE;
+  }
+  ItGeom g;
+  MG_CHECK_ARG(it_geometry(H, W, S, eps, g), "mg_input_transform_windows: %dx%d -> %d needs more than 160 KB of LDS per row band", H, W, S);
+  float* part = reinterpret_cast<float*>(ws);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(itw_minmax_part, dim3(N * 2, MMP), dim3(256), 0, s, base, row_a, row_b, off, part, H, W);
+  static MgPerDevice once;
+  if (mg_first_use_on_device(once))
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&itw_resize_fused), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  hipLaunchKernelGGL(itw_resize_fused, dim3(N * 2, mg_cdiv(g.S, IT_R)), dim3(256), it_lds_floats(g) * sizeof(float), s, base, row_a,
+                     row_b, off, part, out, g);
+  MG_CHECK_LAUNCH("mg_input_transform_windows");
+  return MG_OK;
 }

@@ -17,6 +17,8 @@ from typing import Iterable, List, Optional
 import torch
 import torch.distributed as dist
 
+from .streams import new_stream
+
 
 def is_distributed() -> bool:
     """True when gradients must be exchanged.  MG_FORCE_DP=1 takes the data-parallel code path (side stream, flat bucket,
@@ -48,7 +50,7 @@ class GradBucket:
 
     def _side_stream(self, device) -> torch.cuda.Stream:
         if self._stream is None:
-            self._stream = torch.cuda.Stream(device=device)
+            self._stream = new_stream(device)
         return self._stream
 
     def flat_sink(self, tensors: List[torch.Tensor]):

@@ -9,6 +9,7 @@ from typing import Optional
 import torch
 
 from . import _lib
+from . import streams as _streams
 from ._lib import (MG_C1_LRELU, MG_C1_MASK_AUX, MG_C1_TANH, MG_C1_TANH_BWD_IN, MG_C1_TRANSPOSED, MG_CONV_LRELU,
                    MG_CONV_MASK_AUX, MG_CONV_PIXNORM, MG_CONV_POOL_OUT, MG_CONV_UPS_IN, check)
 
@@ -1416,7 +1417,7 @@ def flac_encode(wav: torch.Tensor, sample_rate: int, bits_per_sample: Optional[i
     # the PCM travels to the host on a side stream and is hashed there while the frames are encoded
     quantised = torch.cuda.Event()
     quantised.record(stream)
-    side = torch.cuda.Stream(dev)
+    side = _streams.new_stream(dev)
     side.wait_event(quantised)
     host_pcm = torch.empty(pcm.numel(), dtype=torch.uint8, pin_memory=True)
     with torch.cuda.stream(side):

@@ -108,7 +108,8 @@ def _latest_state(resume_from: str) -> str:
 def train(run_name: str, input_dataset_path: str, output_dir: str, *, nb_epoch: int = 1000, batch_size: int = 6,
           num_workers: int = 6, metric_every: int = 20, max_iters: int = 0, save_every: int = 1000,
           resume_from: str = None, fadein_lengths=None, train_lengths=None, rand_channels: int = 32,
-          use_packed_loader: bool = True, progress_hook=None, ema_decay: float = 0.0) -> None:
+          use_packed_loader: bool = True, progress_hook=None, ema_decay: float = 0.0, resident: bool = False,
+          random_offset: bool = False) -> None:
     """Reference signature plus keyword-only extensions (all defaulting to the reference's literals).  `resume_from`: a
     directory written by a previous run; its newest `train_state_k.pt` / `gen_k.pt` / `disc_k.pt` / `optim_*_k.pt` set is
     loaded (growth level, Grower counters, weights, Adam state, noise stream, position in the epoch, checkpoint numbering), after
@@ -117,8 +118,29 @@ def train(run_name: str, input_dataset_path: str, output_dir: str, *, nb_epoch: 
     `ema_decay` (0: off): the generator's optimizer keeps an exponential running average of the generator's weights with this
     decay per generator update (Karras et al. 2018 use 0.999), written as `gen_ema_{k}.pt` next to `gen_{k}.pt`; the averages
     travel in `optim_gen_{k}.pt`, so a resumed run continues them, and one resumed from a run without them starts them at the
-    resumed weights.  The critic has no average and training itself does not read the generator's."""
+    resumed weights.  The critic has no average and training itself does not read the generator's.
+    `resident`: the dataset's float32 side-car is uploaded to device memory once (audio.ResidentDataset; under torchrun every rank
+    holds all of it, since any rank may draw any index) and a batch is gathered there, inside the input transform -- the host sends
+    three index vectors per epoch and nothing per batch.  Needs a valid side-car.  `random_offset`: every sample that has a successor
+    in its track is replaced by the 512-frame window starting `o` frames into it and ending `o` frames into the successor, `o`
+    redrawn per sample and epoch (audio.window_offsets: a function of (base seed, epoch, sample), so a resumed or sharded run draws
+    the same windows and no checkpoint carries them).  Needs a side-car with tracks; without `resident` the windows are cut on the
+    host by the packed loader.  Both flags are recorded in `train_state` only so that a resume with other flags is refused."""
     assert isdir(input_dataset_path), f"\"{input_dataset_path}\" doesn't exist or is not a directory"
+    if resident or random_offset:  # what the two flags need, checked before the device is touched
+        if not audio.has_packed(input_dataset_path):
+            raise ValueError(f"resident / random_offset need a valid side-car in \"{input_dataset_path}\": write one with "
+                             f"musicgan_amd.audio.write_packed(path) (resident only) or by running create_dataset again")
+        audio_dataset = audio.PackedAudioDataset(input_dataset_path)
+        if random_offset and audio_dataset.successors() is None:
+            raise ValueError(f"random_offset needs the tracks of the samples, which the side-car in \"{input_dataset_path}\" does "
+                             f"not record: the dataset must be rewritten by create_dataset (single process)")
+    if resume_from is not None:  # (read again below, with everything else of the state)
+        saved = th.load(os.path.join(resume_from, f"train_state_{_latest_state(resume_from)}.pt"))
+        saved_flags = (bool(saved.get("resident", False)), bool(saved.get("random_offset", False)))
+        if saved_flags != (bool(resident), bool(random_offset)):
+            raise ValueError(f"the run in \"{resume_from}\" was trained with resident={saved_flags[0]}, random_offset={saved_flags[1]}; "
+                             f"resuming it with resident={bool(resident)}, random_offset={bool(random_offset)} would not continue it")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -192,11 +214,15 @@ def train(run_name: str, input_dataset_path: str, output_dir: str, *, nb_epoch: 
 
     # the float32 memory-mapped side-car when the dataset has one (one gather + one asynchronous upload per batch on a background
     # thread), the reference's per-sample th.load through DataLoader workers otherwise; same samples in the same order either way
-    use_packed = use_packed_loader and audio.has_packed(input_dataset_path)
-    audio_dataset = audio.PackedAudioDataset(input_dataset_path) if use_packed else audio.AudioDataset(input_dataset_path)
+    use_packed = resident or random_offset or (use_packed_loader and audio.has_packed(input_dataset_path))
+    if not (resident or random_offset):  # (with either flag the packed dataset was opened by the checks at the top)
+        audio_dataset = audio.PackedAudioDataset(input_dataset_path) if use_packed else audio.AudioDataset(input_dataset_path)
     sampler = ShardedShuffle(len(audio_dataset), base_seed, rank, world)
-    if use_packed:
-        data_loader = audio.PackedLoader(audio_dataset, batch_size, sampler, device)
+    if resident:
+        data_loader = audio.ResidentLoader(audio.ResidentDataset(audio_dataset, device), batch_size, sampler, device,
+                                           random_offset=random_offset)
+    elif use_packed:
+        data_loader = audio.PackedLoader(audio_dataset, batch_size, sampler, device, random_offset=random_offset)
     else:
         data_loader = DataLoader(audio_dataset, batch_size=batch_size, sampler=sampler, num_workers=num_workers,
                                  drop_last=True, pin_memory=True)
@@ -233,7 +259,8 @@ def train(run_name: str, input_dataset_path: str, output_dir: str, *, nb_epoch: 
         bar = tqdm(data_loader) if rank == 0 else data_loader
         for x_real in bar:
             # float64 -> float32, per-channel min-max to [-1,1], resize to the current resolution: one fused pass on the GPU
-            x_real = grower.transform_batch(x_real.to(device, non_blocking=True))
+            # (a resident loader's batch is indices into the array on the device: the transform gathers it)
+            x_real = grower.transform_batch(x_real if resident else x_real.to(device, non_blocking=True))
             alpha = grower.alpha
             d = stepper.d_step(x_real, alpha)
             g = stepper.g_step(batch_size, alpha, device) if iter_idx % 5 == 0 else None
@@ -272,7 +299,8 @@ def train(run_name: str, input_dataset_path: str, output_dir: str, *, nb_epoch: 
                     saver.request_save(gen, disc, optim_gen, optim_disc, alpha, train_state=lambda: {
                         "grower": grower.state_dict(), "level": gen.curr_layer, "iter_idx": iter_idx, "epoch": e,
                         "epoch_pos": pos, "base_seed": base_seed, "noise_rng": rng_states, "world": world,
-                        "saver": saver.state_dict_after_save()},
+                        "saver": saver.state_dict_after_save(),
+                        **({"resident": True} if resident else {}), **({"random_offset": True} if random_offset else {})},
                         **({"gen_ema": lambda: optim_gen.averaged_state_dict(gen)} if ema_decay else {}))
                 else:
                     saver.tick()

@@ -30,6 +30,7 @@ import torch
 
 from . import networks
 from .dist import GradBucket, is_distributed
+from .streams import new_stream
 
 
 class ProGANStepper:
@@ -343,7 +344,7 @@ class ProGANStepper:
         if in_line:
             # thread_local: loader threads (pinned-memory staging, uploads on their own stream) keep working during the capture
             # (a capture stream of its own: torch's shared default one would stay broken after an invalidated capture)
-            with torch.cuda.graph(graph, stream=torch.cuda.Stream(device=inputs[0].device), capture_error_mode="thread_local"):
+            with torch.cuda.graph(graph, stream=new_stream(inputs[0].device), capture_error_mode="thread_local"):
                 m = run(FadeIn(alpha, dev=self._fade), *ent["inputs"], captured=True)
                 ent["names"] = list(m.keys())
                 ent["out"] = torch.stack([m[k].reshape(()) for k in ent["names"]])
@@ -351,7 +352,7 @@ class ProGANStepper:
             # data-parallel: TWO graphs sharing one memory pool -- [generator forward] | [everything that reads the critic's
             # weights] -- so that a replay can wait for the critic's exchange + Adam between them instead of in front
             first, pool = torch.cuda.CUDAGraph(), torch.cuda.graph_pool_handle()
-            cap = torch.cuda.Stream(device=inputs[0].device)
+            cap = new_stream(inputs[0].device)
             cap.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(cap):
                 first.capture_begin(pool, capture_error_mode="thread_local")

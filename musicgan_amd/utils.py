@@ -78,9 +78,14 @@ class Grower:
     def scale_transform(self) -> Callable[[torch.Tensor], torch.Tensor]:
         return self._pipeline
 
-    def transform_batch(self, x: torch.Tensor) -> torch.Tensor:
+    def transform_batch(self, x) -> torch.Tensor:
         """`scale_transform(x.to(th.float))` of train.py:139-140.  A batch that already sits on the GPU (float64 as the dataset
-        stores it, or float32) goes through the fused kernel (ops.input_transform); a CPU batch takes the tensor expressions."""
+        stores it, or float32) goes through the fused kernel (ops.input_transform); a CPU batch takes the tensor expressions.  A
+        `WindowBatch` (audio.ResidentLoader: indices into the dataset in device memory) goes through the kernel that gathers while
+        it transforms (window_ops.input_transform_windows)."""
+        if isinstance(x, audio.WindowBatch):
+            from . import window_ops
+            return window_ops.input_transform_windows(x.source, x.rows_a, x.rows_b, x.offsets, self._side())
         if x.is_cuda:
             from . import ops
             return ops.input_transform(x.contiguous(), self._side())
