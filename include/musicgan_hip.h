@@ -738,6 +738,24 @@ int mg_nn_sqdist(const float* q, const float* r, const double* qn, const double*
 int mg_nn_merge(const double* dist, const int64_t* qid, const int64_t* rid, double* best_d, int64_t* best_i, int64_t nq, int64_t nr,
                 int k, mg_stream_t stream);
 
+/* ---- DiffAugment (csrc/diffaug.hip, csrc/diffaug_plan.h): one random translation with zero fill and one random cutout per sample,
+ * applied to every image the critic sees, and the adjoint for the generator's gradient (definition: DESIGN.md 4.13; the kernels behind
+ * musicgan_amd/aug_ops.py).  x, y, gy, gx are (n, c, h, w) float32; u is (n, 8) float32 in [0, 1) in DEVICE memory, read by the kernel:
+ * nothing about it is known to the host, so a captured launch follows whatever u holds when it is replayed.  Columns of u: 0 translation
+ * on iff < p, 1 / 2 its dy / dx, 3 cutout on iff < p, 4 / 5 its centre, 6 / 7 reserved.  ops: MG_DIFFAUG_* bits; 0 <= p <= 1.
+ * fwd:    y = T x.  One launch; any n, c, h, w >= 1; all of y is written.
+ * bwd:    gx = T^t gy, likewise.
+ *         Every output element is a copy of one input element or +0.0 (a select): both are bit-exact, and NaN / inf that the mask or
+ *         the border drops never reach the output.  Source and destination (and u and the destination) must not overlap: MG_EINVAL
+ *         before anything is launched.
+ * decode: HOST only, u in host memory: out[i] = {dy, dx, y0, y1, x0, x1} of sample i -- T x[i, j] = x[i - dy, j - dx], rows [y0, y1) x
+ *         columns [x0, x1) zeroed (all 0: no box) -- through the function the kernels call. */
+#define MG_DIFFAUG_TRANSLATION 1
+#define MG_DIFFAUG_CUTOUT 2
+int mg_diffaug_fwd(const float* x, const float* u, int n, int c, int h, int w, int ops, float p, float* y, mg_stream_t stream);
+int mg_diffaug_bwd(const float* gy, const float* u, int n, int c, int h, int w, int ops, float p, float* gx, mg_stream_t stream);
+int mg_diffaug_decode(const float* u_host, int n, int h, int w, int ops, float p, int32_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@ import re
 from fractions import Fraction
 
 _METRICS = ("swd", "msssim", "nn")
+_AUGMENTS = ("translation", "cutout")   # aug_ops.OPS (not imported here: the modes are dispatched lazily)
 
 
 def _metric_list(text: str):
@@ -22,6 +23,24 @@ def _fraction_list(text: str):
         return tuple(Fraction(t.strip()) for t in text.split(","))
     except (ValueError, ZeroDivisionError):
         raise argparse.ArgumentTypeError(f"a comma-separated list of numbers (a/b or decimals) expected, got {text!r}")
+
+
+def _augment_policy(text: str):
+    """'translation,cutout' as given, once the names are known ones, each given once"""
+    names = tuple(t.strip() for t in text.split(","))
+    if any(n not in _AUGMENTS for n in names) or len(set(names)) != len(names):
+        raise argparse.ArgumentTypeError(f"a comma-separated subset of {','.join(_AUGMENTS)} expected, got {text!r}")
+    return ",".join(names)
+
+
+def _probability(text: str):
+    try:
+        p = float(text)
+    except ValueError:
+        p = -1.0
+    if not 0.0 <= p <= 1.0:
+        raise argparse.ArgumentTypeError(f"a probability in [0, 1] expected, got {text!r}")
+    return p
 
 
 # mode -> (module, function, [(flags, kwargs)], lambda args: positional call arguments[, lambda args: keyword call arguments])
@@ -51,9 +70,15 @@ _MODES = {
         (("--random-offset",), dict(dest="random_offset", action="store_true",
                                     help="train on 512-frame windows at a random time offset into two consecutive chunks of a track, "
                                          "redrawn every epoch (needs a dataset written by create_dataset in one process)")),
+        (("--augment",), dict(type=_augment_policy, default=None, metavar="translation,cutout",
+                              help="DiffAugment: shift (up to 1/8 of each side, zero fill) and / or cut a half-size box out of every "
+                                   "image the critic sees, real and generated; the generator's gradient flows back through it")),
+        (("--augment-p",), dict(dest="augment_p", type=_probability, default=None, metavar="P",
+                                help="probability with which each transform of --augment is applied to a sample (default 1)")),
     ], lambda a: (a.run, a.input_dataset, a.out_path),
         lambda a: {**({"ema_decay": a.ema_decay} if a.ema_decay else {}), **({"resident": True} if a.resident else {}),
-                   **({"random_offset": True} if a.random_offset else {})}),
+                   **({"random_offset": True} if a.random_offset else {}), **({"augment": a.augment} if a.augment else {}),
+                   **({"augment_p": a.augment_p} if a.augment_p is not None else {})}),
     "generate": ("generate", "generate", [
         (("gen_dict_state",), dict(type=str)),
         (("rand_channels",), dict(type=int)),

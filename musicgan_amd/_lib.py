@@ -60,6 +60,7 @@ MG_PACK_CONV3X3, MG_PACK_WINO3X3, MG_PACK_UPCONV3X3, MG_PACK_UPCONV3X3_DGRAD, MG
 MG_SN_LRELU, MG_SN_MASK_AUX, MG_SN_NOLDS = 1, 2, 4
 MG_SN_MAX_OPS = 32
 MG_PCM_F32, MG_PCM_I16, MG_PCM_I32, MG_PCM_U8 = 0, 1, 2, 3
+MG_DIFFAUG_TRANSLATION, MG_DIFFAUG_CUTOUT = 1, 2
 
 
 class SnOp(Structure):
@@ -225,6 +226,9 @@ SIGNATURES = {
     "mg_nn_sqnorm": (c_int, [_P, c_int64, c_int64, _P, _P]),
     "mg_nn_sqdist": (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_int64, _P, _P, c_size_t, _P]),
     "mg_nn_merge": (c_int, [_P, _P, _P, _P, _P, c_int64, c_int64, c_int, _P]),
+    "mg_diffaug_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P]),
+    "mg_diffaug_bwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P]),
+    "mg_diffaug_decode": (c_int, [_P, c_int, c_int, c_int, c_int, c_float, _P]),
 }
 
 _lib = None

@@ -979,18 +979,26 @@ def disc_step_fused(W: DiscWeights, x_real: torch.Tensor, x_fake: torch.Tensor, 
 # Generator step without autograd
 # =====================================================================================================================
 def gen_step_fused(Wg: GenWeights, Wd: DiscWeights, z: torch.Tensor, alpha: float, cache_g: PackCache, cache_d: PackCache,
-                   sink: GradSink, before_disc=None, defer: Optional["ops.WgradDefer"] = None):
+                   sink: GradSink, before_disc=None, defer: Optional["ops.WgradDefer"] = None, augment=None):
     """Gradient of  -mean D(G(z))  (criterion.py:17-18, train.py:191-213) w.r.t. every live generator parameter, written into
     `sink`; returns (gen_loss, out_fake, stats = [mean D(G(z)), gen_loss]).  The critic's weight gradients are not evaluated (the reference computes and discards
     them, train.py:209-214): its backward pass only carries the data gradient down to the generated images.
-    `before_disc` (optional callable) runs between the generator's forward pass and the critic's."""
+    `before_disc` (optional callable) runs between the generator's forward pass and the critic's.
+    `augment` (optional (ops, p, u), u (N, 8) on the device): the critic sees T G(z) (aug_ops.diffaug_fwd) and its input gradient
+    comes back through T^t (aug_ops.diffaug_bwd) -- two launches more."""
     n = z.shape[0]
     x_fake, gctx = gen_forward(Wg, z.contiguous(), alpha, cache_g, save=True)
     if before_disc is not None:  # data-parallel: the critic's weights may still be in flight on the side stream until here
         before_disc()
+    if augment is not None:
+        from .. import aug_ops
+        a_ops, a_p, a_u = augment
+        x_fake = aug_ops.diffaug_fwd(x_fake.contiguous(), a_u, a_ops, a_p)
     out, dctx = disc_forward(Wd, x_fake, alpha, cache_d, save=True)
     g_out = upstream_scores_grad("gen", n, z.device)
     gx, _ = disc_backward(Wd, dctx, g_out, cache_d, None, need_gx=True)
+    if augment is not None:
+        gx = aug_ops.diffaug_bwd(gx.contiguous(), a_u, a_ops, a_p)
     gen_backward(Wg, gctx, gx, cache_g, sink, defer=defer)
     if defer is not None:
         defer.flush()

@@ -109,7 +109,7 @@ def train(run_name: str, input_dataset_path: str, output_dir: str, *, nb_epoch: 
           num_workers: int = 6, metric_every: int = 20, max_iters: int = 0, save_every: int = 1000,
           resume_from: str = None, fadein_lengths=None, train_lengths=None, rand_channels: int = 32,
           use_packed_loader: bool = True, progress_hook=None, ema_decay: float = 0.0, resident: bool = False,
-          random_offset: bool = False) -> None:
+          random_offset: bool = False, augment: str = "", augment_p: float = 1.0) -> None:
     """Reference signature plus keyword-only extensions (all defaulting to the reference's literals).  `resume_from`: a
     directory written by a previous run; its newest `train_state_k.pt` / `gen_k.pt` / `disc_k.pt` / `optim_*_k.pt` set is
     loaded (growth level, Grower counters, weights, Adam state, noise stream, position in the epoch, checkpoint numbering), after
@@ -125,7 +125,16 @@ def train(run_name: str, input_dataset_path: str, output_dir: str, *, nb_epoch: 
     in its track is replaced by the 512-frame window starting `o` frames into it and ending `o` frames into the successor, `o`
     redrawn per sample and epoch (audio.window_offsets: a function of (base seed, epoch, sample), so a resumed or sharded run draws
     the same windows and no checkpoint carries them).  Needs a side-car with tracks; without `resident` the windows are cut on the
-    host by the packed loader.  Both flags are recorded in `train_state` only so that a resume with other flags is refused."""
+    host by the packed loader.  Both flags are recorded in `train_state` only so that a resume with other flags is refused.
+    `augment` ("": off): a comma-separated subset of translation, cutout -- DiffAugment (Zhao et al. 2020): every
+    image the critic sees, real or generated, in both updates, is shifted by up to 1/8 of its sides with zero fill and / or has a
+    half-size box zeroed, each with probability `augment_p` per sample, and the generator's gradient flows back through the transform.
+    The random numbers come from the per-rank noise stream, which is checkpointed, so a resumed run continues them.  Recorded in
+    `train_state` only when on; a resume with other augmentation flags is refused."""
+    aug = networks.DiffAugment(augment, augment_p) if augment else None  # (validated before the device is touched)
+    if aug is None and float(augment_p) != 1.0:
+        raise ValueError(f"augment_p={augment_p!r} without augment: name the transforms, e.g. augment=\"translation,cutout\"")
+    aug_flags = {"augment": aug.policy, "augment_p": aug.p} if aug is not None else {}
     assert isdir(input_dataset_path), f"\"{input_dataset_path}\" doesn't exist or is not a directory"
     if resident or random_offset:  # what the two flags need, checked before the device is touched
         if not audio.has_packed(input_dataset_path):
@@ -141,6 +150,11 @@ def train(run_name: str, input_dataset_path: str, output_dir: str, *, nb_epoch: 
         if saved_flags != (bool(resident), bool(random_offset)):
             raise ValueError(f"the run in \"{resume_from}\" was trained with resident={saved_flags[0]}, random_offset={saved_flags[1]}; "
                              f"resuming it with resident={bool(resident)}, random_offset={bool(random_offset)} would not continue it")
+        saved_aug = {k: saved[k] for k in ("augment", "augment_p") if k in saved}
+        if saved_aug != aug_flags:
+            said = lambda f: f"augment=\"{f['augment']}\", augment_p={f['augment_p']}" if f else "no augmentation"
+            raise ValueError(f"the run in \"{resume_from}\" was trained with {said(saved_aug)}; "
+                             f"resuming it with {said(aug_flags)} would not continue it")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -210,7 +224,8 @@ def train(run_name: str, input_dataset_path: str, output_dir: str, *, nb_epoch: 
         start_iter, start_epoch = int(resume_state["iter_idx"]), int(resume_state["epoch"])
         epoch_pos = int(resume_state["epoch_pos"])
         noise.set_state(resume_state["noise_rng"][rank])
-    stepper = ProGANStepper(gen, disc, optim_gen, optim_disc, rand_channels, height, width, noise=noise)
+    stepper = ProGANStepper(gen, disc, optim_gen, optim_disc, rand_channels, height, width, noise=noise,
+                            **({"augment": aug} if aug is not None else {}))
 
     # the float32 memory-mapped side-car when the dataset has one (one gather + one asynchronous upload per batch on a background
     # thread), the reference's per-sample th.load through DataLoader workers otherwise; same samples in the same order either way
@@ -300,7 +315,8 @@ def train(run_name: str, input_dataset_path: str, output_dir: str, *, nb_epoch: 
                         "grower": grower.state_dict(), "level": gen.curr_layer, "iter_idx": iter_idx, "epoch": e,
                         "epoch_pos": pos, "base_seed": base_seed, "noise_rng": rng_states, "world": world,
                         "saver": saver.state_dict_after_save(),
-                        **({"resident": True} if resident else {}), **({"random_offset": True} if random_offset else {})},
+                        **({"resident": True} if resident else {}), **({"random_offset": True} if random_offset else {}),
+                        **aug_flags},
                         **({"gen_ema": lambda: optim_gen.averaged_state_dict(gen)} if ema_decay else {}))
                 else:
                     saver.tick()

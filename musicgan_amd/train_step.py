@@ -14,6 +14,11 @@ the ~150 launches of an update cost the host one call (the small maps at the end
 of a fade-in, is read by the captured kernels from device memory, so one graph per (level, batch) serves the whole level.
 `MG_GRAPHS=0` disables it.
 
+With `augment` (networks.DiffAugment) every image the critic sees goes through one random translation + cutout T first:
+the real and the generated batch of the critic update (so the penalty is taken at interpolates of the augmented batches), the generated
+batch of the generator update, whose gradient comes back through T^t.  The random numbers u are one more noise input next to z and
+eps: injected, or drawn from the same generator after them, under graphs straight into the static input the captured kernels read.
+
 With torch.distributed initialised (one process per GPU, backend "nccl" = RCCL) the per-rank gradients are summed with one
 flat all-reduce per network on a side stream, the fused Adam runs behind it on that stream, and the main stream meanwhile
 runs the next forward pass that does not depend on the updated weights: every update starts with a forward pass through G (the
@@ -35,11 +40,14 @@ from .streams import new_stream
 
 class ProGANStepper:
     def __init__(self, gen, disc, optim_gen, optim_disc, rand_channels: int, height: int = 2, width: int = 2,
-                 fused_d_step: bool = True, noise: Optional[torch.Generator] = None):
+                 fused_d_step: bool = True, noise: Optional[torch.Generator] = None,
+                 augment: Optional["networks.DiffAugment"] = None):
         """`noise`: device generator the latents and the penalty's epsilon are drawn from when they are not injected (None: the
-        default generator, as the reference does).  Data-parallel runs give every rank its own stream."""
+        default generator, as the reference does).  Data-parallel runs give every rank its own stream.
+        `augment`: a networks.DiffAugment applied to every image the critic sees (None: none, and nothing runs differently)."""
         self.gen, self.disc = gen, disc
         self.noise = noise
+        self.augment = augment
         self.optim_gen, self.optim_disc = optim_gen, optim_disc
         self.rand_channels, self.h, self.w = rand_channels, height, width
         self.fused_d_step = fused_d_step
@@ -66,6 +74,18 @@ class ProGANStepper:
     def _eps_into(self, out: torch.Tensor) -> None:
         torch.rand(out.shape, device=out.device, generator=self.noise, out=out)
 
+    def _u_into(self, out: torch.Tensor) -> None:
+        self.augment.draw(out.shape[0], out.device, generator=self.noise, out=out)
+
+    def _check_u(self, u: Optional[torch.Tensor], rows: int) -> None:
+        if self.augment is None and u is not None:
+            raise ValueError("u was given to a stepper without augmentation")
+        if u is not None and tuple(u.shape) != (rows, 8):
+            raise ValueError(f"u must be ({rows}, 8), got {tuple(u.shape)}")
+
+    def _graph_key_tail(self) -> tuple:
+        return (self.augment.spec,) if self.augment is not None else ()
+
     def _update(self, bucket: GradBucket, net, optim) -> None:
         if self.dp:
             bucket.launch(net.parameters())
@@ -75,8 +95,12 @@ class ProGANStepper:
             optim.step()
 
     def d_step(self, x_real: torch.Tensor, alpha: float, z: Optional[torch.Tensor] = None,
-               eps: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+               eps: Optional[torch.Tensor] = None, u: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """`u` (2N, 8), with augmentation only: rows [0, N) belong to the real batch, rows [N, 2N) to the generated one."""
         n = x_real.shape[0]
+        self._check_u(u, 2 * n)
+        if self.augment is not None:
+            return self._d_step_augmented(x_real, alpha, z, eps, u)
         if self.fused_d_step and self.use_graphs:
             # noise that is not injected is drawn straight into the replayed graph's input buffers (same generator stream, two
             # copy launches fewer per update: at levels 3-4 an update is ~100 launches of 5-20 us)
@@ -111,7 +135,42 @@ class ProGANStepper:
         return {"disc_loss": disc_loss.detach(), "grad_pen": grad_pen.detach(),
                 "out_real_mean": out_real.detach().mean(), "out_fake_mean": out_fake.detach().mean()}
 
-    def _d_step_fused(self, x_real, alpha, z, eps, update_in_line: bool = True, split=None) -> Dict[str, torch.Tensor]:
+    def _d_step_augmented(self, x_real, alpha, z, eps, u) -> Dict[str, torch.Tensor]:
+        """`d_step` with `self.augment`: the same three routes (graphs, fused, modules) on T(x_real), T(G(z)); noise that is not
+        injected is drawn in the order z, eps, u."""
+        n, dev = x_real.shape[0], x_real.device
+        if self.fused_d_step and self.use_graphs:
+            return self._graphed("D", (x_real, z, eps, u), alpha,
+                                 draw=(None, lambda out: self._latent_into(out), lambda out: self._eps_into(out),
+                                       lambda out: self._u_into(out)),
+                                 shapes=(tuple(x_real.shape), (n, self.rand_channels, self.h, self.w), (n, 1, 1, 1), (2 * n, 8)))
+        if z is None:
+            z = self._latent(n, dev)
+        if eps is None:
+            eps = torch.rand(n, 1, 1, 1, device=dev, generator=self.noise)
+        if u is None:
+            u = self.augment.draw(2 * n, dev, generator=self.noise)
+        if self.fused_d_step:
+            return self._d_step_fused(x_real, alpha, z, eps, u=u)
+        if self.dp:
+            self.bucket_d.wait()
+        x_real = self.augment(x_real, u[:n])
+        out_real = self.disc(x_real, alpha)
+        if self.dp:
+            self.bucket_g.wait()
+        with torch.no_grad():
+            x_fake = self.augment(self.gen(z, alpha), u[n:])
+        out_fake = self.disc(x_fake, alpha)
+        disc_loss = networks.wasserstein_discriminator_loss(out_real, out_fake)
+        grad_pen = self.disc.gradient_penalty_with_eps(x_real, x_fake, alpha, eps)
+        self.gen.zero_grad()
+        self.disc.zero_grad()
+        (disc_loss + grad_pen).backward()
+        self._update(self.bucket_d, self.disc, self.optim_disc)
+        return {"disc_loss": disc_loss.detach(), "grad_pen": grad_pen.detach(),
+                "out_real_mean": out_real.detach().mean(), "out_fake_mean": out_fake.detach().mean()}
+
+    def _d_step_fused(self, x_real, alpha, z, eps, update_in_line: bool = True, split=None, u=None) -> Dict[str, torch.Tensor]:
         """Same update as the module path above through `engine.disc_step_fused`: one batched critic pass over
         [real | fake | interpolated] instead of three, one weight-gradient launch per layer.
         Data-parallel: the update has two halves -- the generator's forward pass for the fake batch, which needs G's weights only,
@@ -128,11 +187,19 @@ class ProGANStepper:
         if eager_dp:
             self.bucket_g.wait()  # G's weights final; the critic's exchange + Adam may still be running
         xcat = torch.empty((3 * n,) + tuple(x_real.shape[1:]), dtype=torch.float32, device=dev)
-        xcat[:n].copy_(x_real)
+        if u is None:
+            xcat[:n].copy_(x_real)
+        else:  # T(x_real) in place of the copy
+            from . import aug_ops
+            aug_ops.diffaug_fwd(x_real.contiguous(), u[:n], *self.augment.spec, out=xcat[:n])
         self.gen._pack_cache.refresh(force)
         with torch.no_grad():
-            engine.gen_forward(self.gen._weights(), z.contiguous(), alpha, self.gen._pack_cache, save=False,
-                               out=xcat[n:2 * n])
+            if u is None:
+                engine.gen_forward(self.gen._weights(), z.contiguous(), alpha, self.gen._pack_cache, save=False,
+                                   out=xcat[n:2 * n])
+            else:  # the generated batch through a staging tensor and T: one launch more than without
+                staged, _ = engine.gen_forward(self.gen._weights(), z.contiguous(), alpha, self.gen._pack_cache, save=False)
+                aug_ops.diffaug_fwd(staged.contiguous(), u[n:], *self.augment.spec, out=xcat[n:2 * n])
         if eager_dp:
             self.bucket_d.wait()  # the critic's weights final
         if split is not None:
@@ -152,7 +219,12 @@ class ProGANStepper:
             self._update(self.bucket_d, self.disc, self.optim_disc)
         return {"disc_loss": disc_loss, "grad_pen": grad_pen, "out_real_mean": stats[0], "out_fake_mean": stats[1]}
 
-    def g_step(self, batch_size: int, alpha: float, device, z: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    def g_step(self, batch_size: int, alpha: float, device, z: Optional[torch.Tensor] = None,
+               u: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """`u` (N, 8), with augmentation only."""
+        self._check_u(u, batch_size)
+        if self.augment is not None:
+            return self._g_step_augmented(batch_size, alpha, device, z, u)
         if self.use_graphs:
             return self._graphed("G", (z,), alpha, draw=(lambda out: self._latent_into(out),),
                                  shapes=((batch_size, self.rand_channels, self.h, self.w),), device=device)
@@ -180,7 +252,38 @@ class ProGANStepper:
         self._update(self.bucket_g, self.gen, self.optim_gen)
         return {"gen_loss": gen_loss.detach(), "out_fake_mean": out_fake.detach().mean()}
 
-    def _g_step_fused(self, z, alpha, update_in_line: bool = True, split=None) -> Dict[str, torch.Tensor]:
+    def _g_step_augmented(self, batch_size, alpha, device, z, u) -> Dict[str, torch.Tensor]:
+        """`g_step` with `self.augment`: D sees T(G(z)), the gradient reaches G through T^t; noise not injected is drawn z first, then u."""
+        if self.use_graphs:
+            return self._graphed("G", (z, u), alpha, draw=(lambda out: self._latent_into(out), lambda out: self._u_into(out)),
+                                 shapes=((batch_size, self.rand_channels, self.h, self.w), (batch_size, 8)), device=device)
+        if z is None:
+            z = self._latent(batch_size, device)
+        if u is None:
+            u = self.augment.draw(batch_size, device, generator=self.noise)
+        if self.fused_d_step:
+            return self._g_step_fused(z, alpha, u=u)
+        if self.dp:
+            self.bucket_g.wait()
+        x_fake = self.gen(z, alpha)
+        if self.dp:
+            self.bucket_d.wait()
+        d_params = list(self.disc.parameters())
+        for p in d_params:
+            p.requires_grad_(False)
+        try:
+            out_fake = self.disc(self.augment(x_fake, u), alpha)
+            gen_loss = networks.wasserstein_generator_loss(out_fake)
+            self.gen.zero_grad()
+            self.disc.zero_grad()
+            gen_loss.backward()
+        finally:
+            for p in d_params:
+                p.requires_grad_(True)
+        self._update(self.bucket_g, self.gen, self.optim_gen)
+        return {"gen_loss": gen_loss.detach(), "out_fake_mean": out_fake.detach().mean()}
+
+    def _g_step_fused(self, z, alpha, update_in_line: bool = True, split=None, u=None) -> Dict[str, torch.Tensor]:
         """The generator update through `engine.gen_step_fused` (no autograd graph, no critic weight gradients).  Data-parallel:
         G's forward runs while the critic's gradient exchange + Adam are still on the side stream; the critic's weights (and their
         packed layouts) are only touched behind `bucket_d.wait()` -- eagerly through the waits below, under graph capture
@@ -206,8 +309,9 @@ class ProGANStepper:
         with torch.no_grad():
             Wg, Wd = self.gen._weights(), self.disc._weights()
             sink = engine.GradSink(*self.bucket_g.flat_sink(Wg.tensors())) if self.dp else engine.GradSink()
+            aug = {"augment": (*self.augment.spec, u)} if u is not None else {}
             gen_loss, out, stats = engine.gen_step_fused(Wg, Wd, z, alpha, self.gen._pack_cache, self.disc._pack_cache, sink,
-                                                         before_disc=before_disc, defer=self._defer_g)
+                                                         before_disc=before_disc, defer=self._defer_g, **aug)
         self.gen.zero_grad()
         self.disc.zero_grad()
         for p in Wg.tensors():
@@ -242,7 +346,8 @@ class ProGANStepper:
         net, other = (self.disc, self.gen) if kind == "D" else (self.gen, self.disc)
         opt_sig = (self.optim_disc if kind == "D" else self.optim_gen)
         opt_sig = opt_sig.capture_signature() if hasattr(opt_sig, "capture_signature") else ()
-        key = (kind, self.gen.curr_layer, tuple(tuple(t.shape) for t in inputs), tuple(id(p) for p in net.parameters()), opt_sig)
+        key = (kind, self.gen.curr_layer, tuple(tuple(t.shape) for t in inputs), tuple(id(p) for p in net.parameters()), opt_sig,
+               *self._graph_key_tail())
 
         # Data-parallel: the graph ends with the gradients in the bucket's flat buffer; the exchange (RCCL, side stream) and Adam
         # behind it stay outside, so a replay is bracketed by "join the side streams" and "launch the exchange".
@@ -251,8 +356,8 @@ class ProGANStepper:
         def run(fade, *a, captured=False, split=None):
             upd = in_line or not captured
             if kind == "D":
-                return self._d_step_fused(a[0], fade, a[1], a[2], upd, split)
-            return self._g_step_fused(a[0], fade, upd, split)
+                return self._d_step_fused(a[0], fade, a[1], a[2], upd, split, *a[3:])
+            return self._g_step_fused(a[0], fade, upd, split, *a[1:])
         ent = self._graphs.get(key)
         if ent is None:
             # growth or a new batch shape: graphs of other levels (and their private memory pools, GBs at the large levels)
@@ -324,7 +429,8 @@ class ProGANStepper:
         net = self.disc if kind == "D" else self.gen
         opt = self.optim_disc if kind == "D" else self.optim_gen
         sig = opt.capture_signature() if hasattr(opt, "capture_signature") else ()
-        ent = self._graphs.get((kind, self.gen.curr_layer, tuple(tuple(s) for s in shapes), tuple(id(p) for p in net.parameters()), sig))
+        ent = self._graphs.get((kind, self.gen.curr_layer, tuple(tuple(s) for s in shapes), tuple(id(p) for p in net.parameters()), sig,
+                                *self._graph_key_tail()))
         return ent["inputs"] if ent is not None and "graph" in ent else None
 
     def _capture(self, ent, kind, net, other, inputs, alpha, in_line, run) -> None:
