@@ -3,6 +3,7 @@
 // both networks in ONE launch per optimizer step instead of ~60).
 #pragma once
 #include "mg_common.h"
+#include "wino_plan.h"
 
 constexpr int MG_PACK_CC = 8;  // input channels per LDS chunk (CC / WCC of the convolution kernels)
 
@@ -28,11 +29,7 @@ __host__ __device__ static inline size_t pack_conv3x3_total(int Co, int Ci, int 
 }
 
 // Winograd form U = G g G^T in MFMA operand order (wino3x3.hip); one thread per (chunk, out tile, lane, k-step) = one filter
-__host__ __device__ static inline int pack_wino_nt_padded(int Cout) {
-  const int nt = mg_cdiv(Cout, 16);
-  const int p4 = mg_cdiv(nt, 4) * 4, p3 = mg_cdiv(nt, 3) * 3;
-  return p4 > p3 ? p4 : p3;
-}
+__host__ __device__ static inline int pack_wino_nt_padded(int Cout) { return wino_nt_padded(Cout); }  // (wino_plan.h: the launch goes by the same)
 __device__ __forceinline__ void pack_wino3x3_elem(size_t e, const float* __restrict__ w, float* __restrict__ up, int Co, int Ci,
                                                   int dgrad, int NT) {
   const int cin_call = dgrad ? Co : Ci, cout_call = dgrad ? Ci : Co;

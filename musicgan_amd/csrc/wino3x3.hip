@@ -274,30 +274,51 @@ __global__ void wino3x3_pack_kernel(const float* __restrict__ w, float* __restri
 
 template <int NIW, int WC, int WT>
 int launch_wino(const WinoArgs& a, dim3 grid, hipStream_t s) {
-  constexpr int TPB = WT * 16;
-  constexpr size_t lds = (size_t)(16 * TPB * WCC + WC * NIW * 2048 + WC * TPB * 4) * sizeof(float);
+  constexpr size_t lds = wino_staged_lds(NIW, WC, WT);
   static MgPerDevice once;  // the LDS limit is a per-device function attribute
   if (mg_first_use_on_device(once)) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wino3x3_mfma<NIW, WC, WT>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                              hipFuncAttributeMaxDynamicSharedMemorySize, WINO_LDS_MAX);
   }
   hipLaunchKernelGGL((wino3x3_mfma<NIW, WC, WT>), grid, dim3(64 * WT * WC), lds, s, a);
   MG_CHECK_LAUNCH("mg_wino3x3");
   return MG_OK;
 }
 
-int wino_nt_padded(int Cout) { return pack_wino_nt_padded(Cout); }
-int wino_run(WinoArgs& a, bool pn, hipStream_t s);  // tile geometry + variant dispatch (below)
+int wino_run(WinoArgs& a, hipStream_t s);  // plan (wino_plan.h) + variant dispatch (below)
+
+// The planner's switches from the environment.  Read per entry-point call: tests and A/B runs (tools/tune_wino.py,
+// tools/ab_wino_strip.py, tools/bench_l67.py) switch them inside one process.
+WinoSwitches wino_switches() {
+  WinoSwitches sw;
+  const char* e;
+  auto set = [&e](const char* name) { return (e = getenv(name)) != nullptr; };
+  if (set("MG_WINO_CFG")) sw.cfg = atoi(e);
+  if (set("MG_WINO_WT")) sw.wt = atoi(e);
+  if (set("MG_WINO_NARROW")) sw.narrow = false;
+  if (set("MG_WINO_NARROW_WT")) sw.narrow_wt = atoi(e);
+  if (set("MG_WINO_FEW")) sw.few = atoi(e) != 0;
+  if (set("MG_WINO_PERSIST")) sw.persist = atoi(e) != 0;
+  if (set("MG_WINO_STRIP")) sw.strip = atoi(e) == 0 ? 0 : (atoi(e) > 1 ? 2 : 1);
+  if (set("MG_WINO_STRIP_NIW")) sw.strip_niw = atoi(e);
+  if (set("MG_WINO_STRIP_WGS")) sw.strip_wgs = atoi(e);
+  if (set("MG_WINO_STRIP_PADW")) sw.strip_padw = atof(e);
+  if (set("MG_WINO_STRIP_MIN_BLOCKS")) sw.strip_min_blocks = atoll(e);
+  if (set("MG_WINO_STRIP_ABLATE")) sw.strip_ablate = atoi(e) & 6;
+  return sw;
+}
+
+WinoLayer wino_layer(const WinoArgs& a) { return {a.N, a.Cin, a.Cout, a.H, a.W, a.flags, a.bias != nullptr, a.y != nullptr}; }
 
 }  // namespace
 
 extern "C" size_t mg_wino3x3_packed_floats(int Cin, int Cout) {
-  return (size_t)mg_cdiv(Cin, WCC) * wino_nt_padded(Cout) * 2048;
+  return (size_t)mg_cdiv(Cin, WCC) * pack_wino_nt_padded(Cout) * 2048;
 }
 
 extern "C" int mg_wino3x3_pack(const float* w, float* up, int Co, int Ci, int dgrad, mg_stream_t stream) {
   MG_CHECK_ARG(w && up && Co > 0 && Ci > 0, "mg_wino3x3_pack: bad arguments");
-  const int NT = wino_nt_padded(dgrad ? Ci : Co);
+  const int NT = pack_wino_nt_padded(dgrad ? Ci : Co);
   const size_t total = pack_wino3x3_threads(Co, Ci, dgrad);  // one thread per (chunk, tile, lane, k-step)
   hipLaunchKernelGGL(wino3x3_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, up, Co,
                      Ci, dgrad, NT, total);
@@ -336,106 +357,30 @@ extern "C" int mg_wino3x3(const float* x, const float* up, const float* bias, co
   a.other = nullptr; a.coef = nullptr;
   a.N = N; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W;
   a.flags = flags; a.slope = slope;
-  return wino_run(a, pn, (hipStream_t)stream);
+  return wino_run(a, (hipStream_t)stream);
 }
 
 extern "C" int mg_wino3x3_mask_bytes_y_supported(int N, int Cin, int Cout, int H, int W) {
-  if (N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || (H % 2) || (W % 2)) return 0;
-  WinoArgs a = {};
-  a.N = N; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W;
-  a.flags = MG_CONV_MASK_AUX | MG_CONV_MASK_BYTES;
-  return mgi_wino_strip_takes(a, false) ? 1 : 0;
+  return wino_mask_bytes_y_supported(N, Cin, Cout, H, W, wino_switches()) ? 1 : 0;
 }
 
 namespace {
-int wino_run(WinoArgs& a, bool pn, hipStream_t s) {
-  const int N = a.N, Cin = a.Cin, Cout = a.Cout, H = a.H, W = a.W;
-  const int nt = mg_cdiv(Cout, 16);
-  a.nchunk = mg_cdiv(Cin, WCC);
-  a.NT = wino_nt_padded(Cout);
-  const int Ht = H / 2, Wt = W / 2;
-  // few channels on a large map: one wave per tile block, operands built in registers, filters resident in LDS (wino_strip.hip)
-  if (mgi_wino_strip_takes(a, pn)) return mgi_wino_strip_run(a, s);
-  // (tile-mask bytes applied to a full-resolution result: an epilogue of the strip kernel only -- mg_wino3x3_mask_bytes_y_supported)
-  MG_CHECK_ARG(!(a.flags & MG_CONV_MASK_BYTES) || (a.flags & (MG_CONV_POOL_OUT | WF_BLEND)),
-               "mg_wino3x3: MASK_BYTES without POOL_OUT needs a shape the strip kernel takes (N=%d %d->%d @%dx%d)", N, Cin, Cout, H, W);
-
-  // out-channel tiles per workgroup (wave groups x tiles per wave): 4 = 2x2, 3 = 3x1, 2 = 2x1 -- least padding wins
-  int cfg = 4, best = mg_cdiv(nt, 4) * 4;
-  if (mg_cdiv(nt, 3) * 3 < best) { cfg = 3; best = mg_cdiv(nt, 3) * 3; }
-  if (mg_cdiv(nt, 2) * 2 < best) { cfg = 2; best = mg_cdiv(nt, 2) * 2; }
-  // five or more channel tiles (80 .. 160 out-channels: the 64x64 .. 8x8 layers): two tiles per workgroup in the 32-tile form --
-  // four-wave workgroups, several per CU -- beat the 12- and 16-wave tilings by 6-8 % at 64x64 / 32x32 and by ~20 % at 16x16
-  // (tools/tune_wino.py, every (cfg, wt) per layer shape of a level-5 step); 48 and 64 out-channels stay on their one
-  // workgroup per CU (3x1 and 2x2 tiles)
-  if (nt >= 5) cfg = 2;
-  if (pn) cfg = nt <= 2 ? 2 : (nt == 3 ? 3 : 4);
-  // at most 16 out-channels: ONE channel tile per workgroup and 128 tiles instead of a second, all-padding channel tile
-  // (the 32 -> 16 data gradient at 512x512 spent half its MFMAs on zero filters)
-  const bool narrow = nt == 1 && !pn && getenv("MG_WINO_CFG") == nullptr && getenv("MG_WINO_WT") == nullptr &&
-                      getenv("MG_WINO_NARROW") == nullptr;  // (MG_WINO_NARROW=0: measurement switch, the two-tile forms)
-  if (narrow) cfg = 1;
-  {
-    const char* e = getenv("MG_WINO_CFG");  // measurement override: 2, 3 or 4 out-channel tiles per workgroup
-    if (e != nullptr && !pn) {
-      const int v = atoi(e);
-      if (v == 2 || v == 4 || (v == 3 && mg_cdiv(nt, 3) * 3 <= a.NT)) cfg = v;
-    }
-  }
-  MG_CHECK_ARG(mg_cdiv(nt, cfg) * cfg <= a.NT, "mg_wino3x3: internal tile error");
-  // tiles per workgroup: 64 (one 8..12-wave workgroup per CU: every wave of the CU is in the same phase, so the VALU staging
-  // and epilogue never queue behind another workgroup's matrix instructions -- measured 70..140 cycles per VALU instruction
-  // when they do, tools/hwtests/valu_latency_under_mfma.hip -- and the filters are staged once per 64 tiles) when that still
-  // gives every CU two or more workgroups, else 32 (two workgroups per CU).
-  const int n_cu = mg_cu_count();
-  int wt = ((long long)N * Ht * Wt / 64) * mg_cdiv(nt, cfg) >= 2ll * n_cu ? 4 : 2;
-  if (narrow) {
-    // 32 tiles per two-wave workgroup, ~6 of them per CU: with 16 out-channels a block is a few hundred cycles of MFMAs between
-    // memory round trips, and occupancy hides those where one 128-tile workgroup per CU (the first form of this variant) waited:
-    // 32->16@512, 18 images: 0.70 (two-tile form) -> 0.49 (128 tiles) -> 0.40 ms
-    wt = 2;
-    const char* e = getenv("MG_WINO_NARROW_WT");  // measurement override: 2, 4 or 8 tile groups per workgroup
-    if (e != nullptr && (atoi(e) == 4 || atoi(e) == 8)) wt = atoi(e);
-    if (wt == 8 && (long long)N * Ht * Wt / 128 < 2ll * n_cu) wt = 2;
-  }
-  // two out-channel tiles (<= 32 channels): few MFMAs per staged item and per epilogue, so a block is mostly memory latency and
-  // vector work -- four-wave workgroups, several per CU, overlap that where one eight-wave workgroup per CU waits (measured
-  // 11-16 % on 16->32@512, 32->32@256, 48->32@256; the opposite of the 48- and 64-channel tilings, tools/bench_l67.py)
-  if (cfg == 2 && !narrow && !pn && getenv("MG_WINO_WT") == nullptr && getenv("MG_WINO_CFG") == nullptr) wt = 2;
-  {
-    const char* e = getenv("MG_WINO_WT");  // measurement override
-    if (e != nullptr && (atoi(e) == 2 || atoi(e) == 4)) wt = atoi(e);
-  }
-  // a grid that leaves CUs idle even in the 32-tile form takes two out-channel tiles per workgroup instead of three or four: more,
-  // lighter workgroups (the input tile is staged by more of them, which a half-empty chip does not notice)
-  if (wt == 2 && !pn && cfg > 2 && getenv("MG_WINO_CFG") == nullptr &&
-      ((long long)N * Ht * Wt + 31) / 32 * mg_cdiv(nt, cfg) < n_cu && mg_cdiv(nt, 2) * 2 <= a.NT)
-    cfg = 2;
-  // Few 64-tile blocks per CU (the 48- and 64-channel layers at the reference's batch of 6: 128x128 / 64x64 maps at levels 6-7):
-  // the one-workgroup-per-CU tilings idle through most of their last round and have nobody to overlap their vector phases with;
-  // two out-channel tiles per four-wave workgroup, several per CU, are 5-18 % ahead there (tools/tune_wino.py 6 6 and 7 6:
-  // 64 channels up to 4.5 blocks per CU, 48 channels at 1.5 but not at 4.5; at 16 per CU -- level 5, batch 64 -- the large tilings win)
-  const char* few = getenv("MG_WINO_FEW");  // measurement switch: 0 = keep the large tilings
-  if (!pn && !narrow && getenv("MG_WINO_CFG") == nullptr && getenv("MG_WINO_WT") == nullptr && (few == nullptr || atoi(few) != 0)) {
-    const long long b64 = (long long)N * Ht * Wt / 64;
-    if (((cfg == 4 && b64 < 6ll * n_cu) || (cfg == 3 && 2 * b64 < 5ll * n_cu)) && mg_cdiv(nt, 2) * 2 <= a.NT) {
-      cfg = 2;
-      wt = 2;
-    }
-  }
-  const int tpb = wt * 16;
-  a.TBW = mg_pow2_ceil(Wt) < 16 ? mg_pow2_ceil(Wt) : 16;  // 16 tiles = 32 pixels = one 128-byte line per row and channel
-  a.TBH = mg_pow2_ceil(Ht) < tpb / a.TBW ? mg_pow2_ceil(Ht) : tpb / a.TBW;
-  a.TBN = tpb / (a.TBW * a.TBH);
-  a.lgTBW = mg_ilog2(a.TBW); a.lgTBH = mg_ilog2(a.TBH);
-  a.blocks_x = mg_cdiv(Wt, a.TBW); a.blocks_y = mg_cdiv(Ht, a.TBH); a.blocks_n = mg_cdiv(N, a.TBN);
-  MG_CHECK_ARG((long long)a.TBN * Cin * H * W < (1ll << 29), "mg_wino3x3: image block too large for 32-bit offsets");
-  dim3 grid(a.blocks_x * a.blocks_y * a.blocks_n, mg_cdiv(nt, cfg));
-  {  // persistent launch of the 64-tile form: one workgroup per CU, each walking its tile blocks
-    const char* e = getenv("MG_WINO_PERSIST");  // measurement switch: 0 = one workgroup per tile block
-    if (wt >= 4 && (e == nullptr || atoi(e) != 0) && (int)grid.x > n_cu) grid.x = n_cu;
-  }
-  switch (cfg * 10 + wt) {
+int wino_run(WinoArgs& a, hipStream_t s) {
+  const WinoSwitches sw = wino_switches();
+  const WinoLayer L = wino_layer(a);
+  WinoStripPlan sp = wino_strip_form(L, sw);
+  if (sp.takes) return mgi_wino_strip_run(a, sp, L, sw, s);
+  const WinoStagedPlan p = wino_staged_plan(L, mg_cu_count(), sw);
+  MG_CHECK_ARG(p.status != WINO_MASK_BYTES_SHAPE,
+               "mg_wino3x3: MASK_BYTES without POOL_OUT needs a shape the strip kernel takes (N=%d %d->%d @%dx%d)", a.N, a.Cin, a.Cout,
+               a.H, a.W);
+  MG_CHECK_ARG(p.status != WINO_TILE_ERROR, "mg_wino3x3: internal tile error");
+  MG_CHECK_ARG(p.status != WINO_BLOCK_TOO_LARGE, "mg_wino3x3: image block too large for 32-bit offsets");
+  a.nchunk = p.nchunk; a.NT = p.NT;
+  a.TBW = p.TBW; a.TBH = p.TBH; a.TBN = p.TBN; a.lgTBW = p.lgTBW; a.lgTBH = p.lgTBH;
+  a.blocks_x = p.blocks_x; a.blocks_y = p.blocks_y; a.blocks_n = p.blocks_n;
+  const dim3 grid(p.grid_x, p.grid_y);
+  switch (p.cfg * 10 + p.wt) {  // <tiles per wave, wave groups, tile groups>: the nine instantiations
     case 18: return launch_wino<1, 1, 8>(a, grid, s);
     case 14: return launch_wino<1, 1, 4>(a, grid, s);
     case 12: return launch_wino<1, 1, 2>(a, grid, s);
@@ -444,8 +389,10 @@ int wino_run(WinoArgs& a, bool pn, hipStream_t s) {
     case 34: return launch_wino<1, 3, 4>(a, grid, s);
     case 32: return launch_wino<1, 3, 2>(a, grid, s);
     case 24: return launch_wino<1, 2, 4>(a, grid, s);
-    default: return launch_wino<1, 2, 2>(a, grid, s);
+    case 22: return launch_wino<1, 2, 2>(a, grid, s);
   }
+  mg_set_error("mg_wino3x3: no kernel for %d out-channel tiles x %d tile groups per workgroup", p.cfg, p.wt);
+  return MG_EINVAL;
 }
 }  // namespace
 
@@ -470,5 +417,5 @@ extern "C" int mg_wino3x3_fade(const float* x, const float* up, const float* bia
   a.flags = mode == MG_FADE_FWD ? (WF_BLEND | MG_CONV_LRELU)
           : mode == MG_FADE_TANGENT ? (WF_BLEND | MG_CONV_MASK_AUX | MG_CONV_MASK_BYTES) : WF_BLEND_BWD;
   a.slope = slope;
-  return wino_run(a, false, (hipStream_t)stream);
+  return wino_run(a, (hipStream_t)stream);
 }

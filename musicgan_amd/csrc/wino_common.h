@@ -1,7 +1,10 @@
 // Shared pieces of the Winograd F(2x2,3x3) convolution kernels (wino3x3.hip: LDS-staged tile blocks; wino_strip.hip: one wave per
 // tile block, operands built in registers): launch arguments, packed-subtraction helper, internal epilogue selectors.
 #pragma once
+#include <cstddef>
+
 #include "mg_common.h"
+#include "wino_plan.h"
 
 // (global: wino3x3.hip hands its arguments to wino_strip.hip)
 struct WinoArgs {
@@ -24,13 +27,16 @@ struct WinoArgs {
   const float* other;       // fade-in forms: the old branch (forward / tangent) or its activation (backward)
   const float* coef;        // fade-in forms: {alpha, 1 - alpha} in device memory
 };
+// (the layout the kernels read: the strip kernel finds its grid in the geometry fields, launch_strip in wino_strip.hip)
+static_assert(sizeof(WinoArgs) == 160 && offsetof(WinoArgs, N) == 56 && offsetof(WinoArgs, TBW) == 84 &&
+              offsetof(WinoArgs, blocks_x) == 104 && offsetof(WinoArgs, NT) == 120 && offsetof(WinoArgs, mi) == 128);
 
-bool mgi_wino_strip_takes(const WinoArgs& a, bool pn);  // wino_strip.hip
-int mgi_wino_strip_run(WinoArgs& a, hipStream_t s);
+// the strip kernel (wino_strip.hip) on a call whose plan says p.takes: its grid (p is completed) and the launch
+int mgi_wino_strip_run(WinoArgs& a, WinoStripPlan& p, const WinoLayer& L, const WinoSwitches& sw, hipStream_t s);
 
 namespace {
 
-constexpr int WCC = 8;  // input channels per LDS chunk
+constexpr int WCC = WINO_CC;  // input channels per LDS chunk
 constexpr float PN_EPS = 1e-8f;
 
 // Packed fp32 subtraction as ONE instruction (hipcc lowers vector subtraction to one v_sub_f32 per element; fp32 MFMA and VALU
@@ -46,10 +52,5 @@ __device__ __forceinline__ f32x4 pk_sub4(f32x4 x, f32x4 y) {
   const wf32x2 hi = pk_sub(__builtin_shufflevector(x, x, 2, 3), __builtin_shufflevector(y, y, 2, 3));
   return f32x4{lo[0], lo[1], hi[0], hi[1]};
 }
-
-
-// internal epilogue selectors of mg_wino3x3_fade (above the public MG_CONV_* bits)
-constexpr int WF_BLEND = 1 << 8;      // y = coef[0] * result + coef[1] * other
-constexpr int WF_BLEND_BWD = 1 << 9;  // y = (coef[0] * acc) * lrelu'(mi),  p = (coef[1] * acc) * lrelu'(other)
 
 }  // namespace

@@ -28,7 +28,7 @@
 // them the MFMA reads the old register contents (wrong sums, no fault).  The packed transforms below therefore end in `s_nop`.
 // The same holds the other way round (inline-assembly vector instructions that READ MFMA results: the output transform), and a
 // third rule: 16-byte buffer stores with a scalar soffset need a wait state before their data registers are overwritten (below).
-#include <cstdlib>
+#include <mutex>
 #include <type_traits>
 #include <utility>
 
@@ -41,19 +41,6 @@ namespace {
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-enum StripKind {
-  SK_ACT = 0,        // bias + LeakyReLU -> y (+ pooled)
-  SK_ACT_POOL_MOUT,  // bias + LeakyReLU -> pooled + tile-mask bytes (y never written)
-  SK_MB_POOL,        // x tile-mask bytes -> pooled
-  SK_MASKF,          // x fp32 LeakyReLU mask of aux -> y (+ pooled)
-  SK_UNPOOL,         // 0.25 * up2(result) x mask bytes of the layer below -> y at twice the size
-  SK_BLEND_FWD,      // fade-in forward: act, tile mask out, alpha * new + (1 - alpha) * old -> y
-  SK_BLEND_TAN,      // fade-in tangent: x mask bytes, blend -> y
-  SK_BLEND_BWD,      // fade-in backward: two masked, scaled copies -> y, p
-  SK_PN,             // bias + LeakyReLU + PixelNorm -> p, rn (+ y)
-  SK_MB_Y,           // x tile-mask bytes -> y (a data gradient times the LeakyReLU derivative of the layer below, kept as bytes)
-};
 
 // (by value on purpose: __builtin_bit_cast applied to an ext-vector ELEMENT lvalue, e.g. bit_cast(unsigned, v4[g]), reads element 0
 // whatever g is -- clang 19 / ROCm 7.2; found as "every out-channel of a lane gets channel 0's pooled value")
@@ -613,158 +600,69 @@ __global__ void __launch_bounds__(64 * NWAVE, (NIW == 1 && KIND != SK_UNPOOL && 
   else strip_body<NIW, NIW, NWAVE, KIND, POOL>(a, row * NIW, wg, g_full);
 }
 
+// Workgroups per CU of an instantiation at an LDS size, as hipOccupancyMaxActiveBlocksPerMultiprocessor says: a runtime call of
+// microseconds, asked once per (device, LDS size).  Host threads may launch concurrently, on different devices and layers: the table
+// is read and extended under its mutex, so no reader sees a half-written entry and two writers never share a slot (a full table
+// only means the query is repeated).
 template <int NIW, int NWAVE, int KIND, bool POOL>
-int launch_strip(const WinoArgs& a, dim3 grid, hipStream_t s) {
-  const size_t lds = (size_t)a.nchunk * NIW * 2048 * sizeof(float);
-  static MgPerDevice once;
-  const void* fn = reinterpret_cast<const void*>(&wino3x3_strip<NIW, NWAVE, KIND, POOL>);
-  if (mg_first_use_on_device(once)) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  // persistent workgroups: as many per CU as registers and the filter bank's LDS allow (the one-tile kernels: two, i.e. four waves
-  // per SIMD -- the waves are independent, occupancy is what hides a block's load latency), never more than there are groups
-  // (the occupancy query is a runtime call of microseconds: asked once per (device, LDS size) of this instantiation -- benign race:
-  // every thread computes the same value)
+int strip_occupancy(const void* fn, size_t lds) {
+  static std::mutex m;
   static struct { int dev; size_t lds; int v; } occ[8];
   static int nocc = 0;
-  int per_cu = 0;
   const int dev = mg_current_device();
-  for (int i = 0; i < nocc && i < 8; ++i)
-    if (occ[i].dev == dev && occ[i].lds == lds) per_cu = occ[i].v;
-  if (per_cu == 0) {
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * NWAVE, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-    if (per_cu > 16 / NWAVE) per_cu = 16 / NWAVE;
-    if (nocc < 8) { occ[nocc].dev = dev; occ[nocc].lds = lds; occ[nocc].v = per_cu; ++nocc; }
-  }
-  {
-    const char* e = getenv("MG_WINO_STRIP_WGS");  // measurement switch (tools/ab_wino_strip.py flips it inside one process): workgroups per CU
-    if (e != nullptr && atoi(e) >= 1) per_cu = atoi(e);
-  }
-  // rows of workgroups (grid.y of the caller = number of rows) laid out in a 1-D grid; a last row whose second tile is padding does
-  // ~0.7 of a full row's work (half the MFMAs and epilogue, the same input loads and transform; swept 0.6 .. 1.0 on 64->48@128,
-  // 64->80@64, 48->48@128: 0.7) and gets that share of the workgroups
-  const int rows = (int)grid.y, nt = a.Cout / 16;
-  const bool has_pad = NIW == 2 && (nt & 1) != 0 && rows > 1;
-  const int total = per_cu * mg_cu_count();
-  static const double pad_w = getenv("MG_WINO_STRIP_PADW") ? atof(getenv("MG_WINO_STRIP_PADW")) : 0.7;
-  int g_pad = 0, g_full;
-  if (has_pad) {
-    g_pad = (int)(total * pad_w / ((rows - 1) + pad_w)) & ~7;
-    if (g_pad < 8) g_pad = 8;
-    g_full = ((total - g_pad) / (rows - 1)) & ~7;
-  } else {
-    g_full = (total / rows) & ~7;
-  }
-  if (g_full < 8) g_full = 8;
-  const int nitems = a.N * (a.blocks_y / NWAVE) * a.blocks_x;
-  if (g_full > nitems) g_full = nitems;  // (small launches: fewer workgroups than CUs; the XCD mapping then is whatever it is)
-  if (g_pad > nitems) g_pad = nitems;
+  std::lock_guard<std::mutex> lock(m);
+  for (int i = 0; i < nocc; ++i)
+    if (occ[i].dev == dev && occ[i].lds == lds) return occ[i].v;
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * NWAVE, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+  if (nocc < 8) occ[nocc++] = {dev, lds, per_cu};
+  return per_cu;
+}
+
+template <int NIW, int NWAVE, int KIND, bool POOL>
+int launch_strip(const WinoArgs& a, WinoStripPlan& p, const WinoLayer& L, const WinoSwitches& sw, hipStream_t s) {
+  static MgPerDevice once;
+  const void* fn = reinterpret_cast<const void*>(&wino3x3_strip<NIW, NWAVE, KIND, POOL>);
+  if (mg_first_use_on_device(once)) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, WINO_LDS_MAX);
+  wino_strip_grid(p, L, mg_cu_count(), strip_occupancy<NIW, NWAVE, KIND, POOL>(fn, p.lds), sw);
+  // The strip kernel has no tile-block geometry of its own and reads the grid's layout and the ablation bits from those fields of
+  // WinoArgs instead: TBW = workgroups per full row, TBH = workgroups of the padding row (0: none), lgTBW = rows, TBN bits 1-2 = ablation
   WinoArgs b = a;
-  b.TBW = g_full; b.TBH = g_pad; b.lgTBW = rows;
-  grid = dim3((unsigned)((rows - (g_pad ? 1 : 0)) * g_full + g_pad), 1, 1);
-  hipLaunchKernelGGL((wino3x3_strip<NIW, NWAVE, KIND, POOL>), grid, dim3(64 * NWAVE), lds, s, b);
+  b.TBW = p.g_full; b.TBH = p.g_pad; b.lgTBW = p.rows; b.TBN |= p.ablate;
+  hipLaunchKernelGGL((wino3x3_strip<NIW, NWAVE, KIND, POOL>), dim3((unsigned)p.grid, 1, 1), dim3(64 * NWAVE), p.lds, s, b);
   MG_CHECK_LAUNCH("mg_wino3x3 (strip)");
   return MG_OK;
 }
 
 template <int NIW, int NWAVE>
-int launch_strip_kind(const WinoArgs& a, int kind, dim3 grid, hipStream_t s) {
-  const bool pool = (a.flags & MG_CONV_POOL_OUT) != 0;
-  switch (kind) {
-    case SK_ACT: return pool ? launch_strip<NIW, NWAVE, SK_ACT, true>(a, grid, s) : launch_strip<NIW, NWAVE, SK_ACT, false>(a, grid, s);
-    case SK_ACT_POOL_MOUT: return launch_strip<NIW, NWAVE, SK_ACT_POOL_MOUT, true>(a, grid, s);
-    case SK_MB_POOL: return launch_strip<NIW, NWAVE, SK_MB_POOL, true>(a, grid, s);
-    case SK_MASKF: return pool ? launch_strip<NIW, NWAVE, SK_MASKF, true>(a, grid, s) : launch_strip<NIW, NWAVE, SK_MASKF, false>(a, grid, s);
-    case SK_UNPOOL: return launch_strip<NIW, NWAVE, SK_UNPOOL, false>(a, grid, s);
-    case SK_BLEND_FWD: return launch_strip<NIW, NWAVE, SK_BLEND_FWD, false>(a, grid, s);
-    case SK_BLEND_TAN: return launch_strip<NIW, NWAVE, SK_BLEND_TAN, false>(a, grid, s);
-    case SK_BLEND_BWD: return launch_strip<NIW, NWAVE, SK_BLEND_BWD, false>(a, grid, s);
-    case SK_MB_Y: return launch_strip<NIW, NWAVE, SK_MB_Y, false>(a, grid, s);
+int launch_strip_kind(const WinoArgs& a, WinoStripPlan& p, const WinoLayer& L, const WinoSwitches& sw, hipStream_t s) {
+  const bool pool = p.pool;
+  switch (p.kind) {
+    case SK_ACT: return pool ? launch_strip<NIW, NWAVE, SK_ACT, true>(a, p, L, sw, s) : launch_strip<NIW, NWAVE, SK_ACT, false>(a, p, L, sw, s);
+    case SK_ACT_POOL_MOUT: return launch_strip<NIW, NWAVE, SK_ACT_POOL_MOUT, true>(a, p, L, sw, s);
+    case SK_MB_POOL: return launch_strip<NIW, NWAVE, SK_MB_POOL, true>(a, p, L, sw, s);
+    case SK_MASKF: return pool ? launch_strip<NIW, NWAVE, SK_MASKF, true>(a, p, L, sw, s) : launch_strip<NIW, NWAVE, SK_MASKF, false>(a, p, L, sw, s);
+    case SK_UNPOOL: return launch_strip<NIW, NWAVE, SK_UNPOOL, false>(a, p, L, sw, s);
+    case SK_BLEND_FWD: return launch_strip<NIW, NWAVE, SK_BLEND_FWD, false>(a, p, L, sw, s);
+    case SK_BLEND_TAN: return launch_strip<NIW, NWAVE, SK_BLEND_TAN, false>(a, p, L, sw, s);
+    case SK_BLEND_BWD: return launch_strip<NIW, NWAVE, SK_BLEND_BWD, false>(a, p, L, sw, s);
+    case SK_MB_Y: return launch_strip<NIW, NWAVE, SK_MB_Y, false>(a, p, L, sw, s);
     default:
-      if constexpr (NIW <= 2) return launch_strip<NIW, NWAVE, SK_PN, false>(a, grid, s);
+      if constexpr (NIW <= 2) return launch_strip<NIW, NWAVE, SK_PN, false>(a, p, L, sw, s);
       mg_set_error("mg_wino3x3 (strip): PixelNorm with three out-channel tiles");
       return MG_EINVAL;
   }
 }
 
-// Out-channel tiles per wave for a layer of nt tiles, or 0 = leave the call to wino3x3.hip.  Two wherever there are two or more (128
-// accumulators, two waves per SIMD; further tile pairs go to further workgroup rows, which read and transform the input again; an odd
-// count ends in a row that computes ONE tile on the two-tile filter image and gets a smaller share of the grid), one for 16
-// out-channels.  The choice follows tools/ab_wino_strip.py (profiles/r05_ab_wino_strip.txt), us per launch against wino3x3.hip:
-// 32 channels 0.72-0.92;  64 channels (the dominant launches of level 5: 48->64 @128 x 192 images 929 -> 782) 0.81-0.94;  48 channels
-// 0.73-0.96 (64->48 @128 x 192, the largest launch of a level-5 step: 1016 -> 903);  80 / 96 channels 0.78-0.97 -- each from ~2 000
-// tile blocks on (whole steps: 4096 -> 2048 is -0.3 % at level 5, -0.5 % at level 4, nothing at levels 3 / 6 / 7; 1536 is +1.3 % at level 6);  16 channels (one tile per wave: the 32 -> 16 data gradient of level 7) 0.81-0.91 since the in-block halo pixels come
-// by DPP (1.01-1.06 before).  `force` (MG_WINO_STRIP=2: tests, A/B): whatever the shape allows.  MG_WINO_STRIP_NIW (1 / 2 / 3) overrides the tile count per wave (3: the 192-accumulator, one-wave-per-SIMD
-// form for exactly 48 channels; measurements).
-long long strip_min_blocks() {
-  static const long long v = getenv("MG_WINO_STRIP_MIN_BLOCKS") ? atoll(getenv("MG_WINO_STRIP_MIN_BLOCKS")) : 2048;
-  return v;
-}
-
-int strip_plan(const WinoArgs& a, bool pn, bool force) {
-  const int nt = a.Cout / 16;
-  const long long blocks = (long long)a.N * (a.H / 2) * (a.W / 32);
-  int niw = 0;
-  niw = (force || blocks >= strip_min_blocks()) ? (nt == 1 ? 1 : 2) : 0;
-  // 96 .. 160 input channels: the filter bank of TWO out-channel tiles does not fit the LDS (8 KB per 8-channel chunk and tile), that
-  // of one does -- one tile per wave then (the input is read and transformed once per tile, and still 0.82 of the staged kernel's time:
-  // 96 -> 80 @32 x 192 images 168 -> 138 us, profiles/r06_ab_strip_small.txt)
-  if (niw == 2 && (size_t)(a.Cin / WCC) * 2 * 8192 > 160 * 1024) niw = 1;
-  if (pn) niw = nt <= 2 ? (niw ? nt : 0) : 0;  // PixelNorm: all channels of a pixel in one wave
-  const char* e = getenv("MG_WINO_STRIP_NIW");
-  if (e != nullptr && !pn && niw != 0) {
-    const int v = atoi(e);
-    if (v == 1 || (v == 2 && nt >= 2) || (v == 3 && nt == 3)) niw = v;
-  }
-  return niw;
-}
-
-int strip_kind(const WinoArgs& a) {  // the dispatch of wino_epilogue.h, by name
-  if (a.flags & MG_CONV_PIXNORM) return SK_PN;
-  if (a.flags & MG_CONV_UNPOOL) return SK_UNPOOL;
-  if (a.flags & WF_BLEND_BWD) return SK_BLEND_BWD;
-  if (a.flags & WF_BLEND) return (a.flags & MG_CONV_MASK_BYTES) ? SK_BLEND_TAN : SK_BLEND_FWD;
-  if (a.flags & MG_CONV_MASK_AUX) return (a.flags & MG_CONV_MASK_BYTES) ? ((a.flags & MG_CONV_POOL_OUT) ? SK_MB_POOL : SK_MB_Y) : SK_MASKF;
-  return (a.flags & MG_CONV_MASK_OUT) ? SK_ACT_POOL_MOUT : SK_ACT;
-}
-
 }  // namespace
 
-// Whether wino_run (wino3x3.hip) hands this call to the strip kernel.  Shape: whole 16-channel chunk pairs and out tiles, whole 16-tile
-// blocks per tile row, whole groups of 8 tile rows, the filter bank of a workgroup's tiles within LDS, every plane within 32-bit byte
-// offsets, masked kinds bias-free, PixelNorm without y; then strip_plan's choice.  MG_WINO_STRIP=0: never; =2: whenever the shape allows.
-bool mgi_wino_strip_takes(const WinoArgs& a, bool pn) {
-  const char* e = getenv("MG_WINO_STRIP");
-  if (e != nullptr && atoi(e) == 0) return false;
-  const int nt = a.Cout / 16;
-  if ((a.Cin % 16) != 0 || (a.Cout % 16) != 0 || nt > 10 || (a.W % 32) != 0 || ((a.H / 2) % 8) != 0 || (a.H % 2) != 0) return false;
-  if (pn && (nt > 2 || a.y != nullptr)) return false;  // (PixelNorm: all channels of a pixel in one wave, p and rn only)
-  if ((a.flags & (MG_CONV_MASK_AUX | MG_CONV_UNPOOL | WF_BLEND_BWD)) && a.bias != nullptr) return false;  // masked kinds: bias-free
-  if ((long long)a.Cout * a.H * a.W * 16 >= (1ll << 31) || (long long)a.Cin * a.H * a.W * 4 >= (1ll << 31)) return false;
-  const int niw = strip_plan(a, pn, e != nullptr && atoi(e) > 1);
-  return niw != 0 && (size_t)(a.Cin / WCC) * niw * 8192 <= 160 * 1024;  // the filter bank of a workgroup's tiles fits LDS
-}
-
-int mgi_wino_strip_run(WinoArgs& a, hipStream_t s) {
-  const int nt = a.Cout / 16;
-  a.nchunk = a.Cin / WCC;
-  a.NT = pack_wino_nt_padded(a.Cout);
-  a.TBW = 16; a.TBH = 1; a.TBN = 1; a.lgTBW = 4; a.lgTBH = 0;
-  {
-    // measurement switch (ablation): 2 = every input row through a zero-record descriptor (reads return 0, nothing is fetched),
-    // 4 = every epilogue access likewise (stores dropped, masks read as 0), 6 = both: what is left is issue time
-    const char* e = getenv("MG_WINO_STRIP_ABLATE");
-    if (e != nullptr) a.TBN |= atoi(e) & 6;
-  }
-  a.blocks_x = a.W / 32; a.blocks_y = a.H / 2; a.blocks_n = a.N;
-  // out-channel tiles per wave: all of them (NIW = nt: the input transform is done once) or ONE with the tiles on grid.y (half
-  // the registers, twice the waves per SIMD, the input read and transformed once per tile); PixelNorm needs all channels in a wave
-  const int kind = strip_kind(a);
-  const char* e = getenv("MG_WINO_STRIP");
-  const int niw = strip_plan(a, kind == SK_PN, e != nullptr && atoi(e) > 1);
-  dim3 grid(1, mg_cdiv(nt, niw));  // (an odd tile count: the last workgroup row carries one padding tile of zero filters)
-  switch (niw) {
-    case 1: return launch_strip_kind<1, 8>(a, kind, grid, s);  // (four-wave workgroups, i.e. up to four waves per SIMD: no effect,
-                                                               //  profiles/r05_ab_wino_strip_nt1_occupancy.txt)
-    case 2: return launch_strip_kind<2, 8>(a, kind, grid, s);
-    default: return launch_strip_kind<3, 4>(a, kind, grid, s);
+int mgi_wino_strip_run(WinoArgs& a, WinoStripPlan& p, const WinoLayer& L, const WinoSwitches& sw, hipStream_t s) {
+  a.nchunk = p.nchunk; a.NT = p.NT;
+  a.TBN = 1; a.lgTBH = 0;  // (a block is 16 x 1 x 1 tiles; TBW, TBH and lgTBW carry the grid: launch_strip)
+  a.blocks_x = p.blocks_x; a.blocks_y = p.blocks_y; a.blocks_n = a.N;
+  switch (p.niw) {
+    case 1: return launch_strip_kind<1, 8>(a, p, L, sw, s);
+    case 2: return launch_strip_kind<2, 8>(a, p, L, sw, s);
+    default: return launch_strip_kind<3, 4>(a, p, L, sw, s);
   }
 }

@@ -129,3 +129,51 @@ def test_strip_kernel_against_fp64_at_level_6_7_shapes(shape, monkeypatch):
     # the same with the mask as one byte per 2x2 tile (what the critic keeps of its stem's output): the same bits
     gxb = ops.conv3x3(gy.to(DEV), None, None, ci, mask_aux=_tile_mask(x.to(DEV)), wino=ops.pack_wino3x3(wt.to(DEV), dgrad=True))
     assert torch.equal(gx, gxb)
+
+
+# (N, Cin, Cout, H, W): taken and declined for each reason -- ragged channels, too few tile rows, W not a multiple of 32 --, the
+# one-tile-per-wave filter banks, and a level-7 layer (shape arithmetic only: nothing is allocated)
+PLAN_SHAPES = [(1, 16, 16, 16, 32), (1, 16, 32, 8, 32), (1, 8, 32, 16, 32), (1, 16, 32, 16, 48), (2, 96, 80, 32, 32), (1, 112, 96, 16, 32),
+               (18, 16, 32, 512, 512)]
+
+
+def test_the_library_launches_what_the_cpu_planner_plans(monkeypatch, tmp_path_factory):
+    """csrc/wino_plan.h as tests/test_wino_plan_cpu.py compiles it and as the library was built with it: the same answers on this
+    device, and the two plans whose grid arithmetic is at its edge launch and give the staged kernel's bits."""
+    import numpy as np
+    import wino_plan_shim as shim
+    ops = _ops()
+    lib = shim.load(tmp_path_factory.mktemp("wino_plan"))
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    for mode in (None, "0", "2"):
+        if mode is None:
+            monkeypatch.delenv("MG_WINO_STRIP", raising=False)
+        else:
+            monkeypatch.setenv("MG_WINO_STRIP", mode)
+        sw = shim.switches(lib, **({} if mode is None else {"strip": int(mode)}))
+        layers = np.array([(*s, shim.FLAGS["MASK_AUX"] | shim.FLAGS["MASK_BYTES"], 0, 1) for s in PLAN_SHAPES])
+        want = [bool(v) for v in shim.plan(lib, layers, n_cu, 1, sw).mask_bytes_y]
+        assert [ops.wino3x3_mask_bytes_y_supported(*s) for s in PLAN_SHAPES] == want, mode
+        assert mode != "0" or not any(want)
+        assert mode != "2" or want == [True, False, False, False, True, True, True]
+
+    g = torch.Generator(device=DEV).manual_seed(41)
+    R = lambda *s: torch.randn(*s, device=DEV, generator=g)
+    # (shape, switches, the plan's edge): one item, a padding row, g_full and g_pad clamped to the item count; the four-wave form
+    for (n, ci, co, h, w), env, edge in (((1, 16, 48, 16, 32), {"MG_WINO_STRIP": "2"}, dict(niw=2, nwave=8, rows=2, g_full=1, g_pad=1, grid=2)),
+                                         ((1, 48, 48, 16, 32), {"MG_WINO_STRIP": "2", "MG_WINO_STRIP_NIW": "3"},
+                                          dict(niw=3, nwave=4, rows=1, g_full=2, g_pad=0, grid=2))):
+        sw = shim.switches(lib, strip=2, strip_niw=int(env.get("MG_WINO_STRIP_NIW", 0)))
+        for per_cu in (1, 2, 4):  # whatever the occupancy query says here
+            p = shim.plan(lib, np.array([(n, ci, co, h, w, shim.FLAGS["LRELU"], 1, 1)]), n_cu, per_cu, sw)
+            assert p.strip[0] == 1 and {k: int(getattr(p, k)[0]) for k in edge} == edge
+        x, wt, b = R(n, ci, h, w), R(co, ci, 3, 3) / math.sqrt(9 * ci), R(co)
+        up = ops.pack_wino3x3(wt, dgrad=False)
+        monkeypatch.setenv("MG_WINO_STRIP", "0")
+        monkeypatch.delenv("MG_WINO_STRIP_NIW", raising=False)
+        staged = ops.conv3x3(x, None, b, co, lrelu=True, wino=up)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        strip = ops.conv3x3(x, None, b, co, lrelu=True, wino=up)
+        monkeypatch.delenv("MG_WINO_STRIP_NIW", raising=False)
+        assert torch.equal(staged, strip), f"{(n, ci, co, h, w)}: {int((staged != strip).sum())} of {staged.numel()} elements differ"
