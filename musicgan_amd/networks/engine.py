@@ -20,7 +20,8 @@ Gradient penalty  P = 10 * mean_n (||g_0[n]|| - 1)^2,  g_0 = d D(x~) / d x~  (fi
 from __future__ import annotations
 
 import os
-from typing import Dict, List, Optional
+from dataclasses import dataclass
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -123,7 +124,7 @@ class PackCache:
     @staticmethod
     def small_ok(x: torch.Tensor, cout: int, **kw) -> bool:
         """Whether `conv` routes this call to ops.conv3x3_small: supported epilogue (no PixelNorm / tile masks), output map within
-        MG_SMALLCONV_MAX_SIDE (default 8) and few enough pixels to be latency-bound (MG_SMALLCONV_MAX_PIXELS, default 3072 up to 4x4, 2048 at 8x8)."""
+        MG_SMALLCONV_MAX_SIDE (default 16) and few enough pixels to be latency-bound (MG_SMALLCONV_MAX_PIXELS, default 3072 up to 4x4, 2048 at 8x8)."""
         if kw.get("pixnorm") or kw.get("mask_out") or kw.get("unpool_mask") is not None or kw.get("want_y", True) is False:
             return False
         m = kw.get("mask_aux")
@@ -266,6 +267,11 @@ def _smallnet_on() -> bool:
     return os.environ.get("MG_SMALLNET", "0") == "1"
 
 
+def _tilemask_on() -> bool:
+    """MG_TILEMASK=0: the critic keeps fp32 activations everywhere (no uint8 tile masks, no fade-in blend in a conv epilogue)."""
+    return os.environ.get("MG_TILEMASK", "1") != "0"
+
+
 def _imgs_per_wg(n: int) -> int:
     """One image per workgroup while every image still gets a CU of its own (shortest chain); two beyond that (half the
     filter traffic per image)."""
@@ -319,6 +325,32 @@ class GradSink:
     def get(self, param: torch.Tensor) -> Optional[torch.Tensor]:
         return self.g.get(id(param))
 
+    # One launch per gradient kind into the slots of a layer's weight and bias (taken in that order): `accumulate` comes from the
+    # weight's slot, `b=None` leaves the bias gradient out (the penalty reaches no bias), `kw` goes to the launch as given.
+    def _slots(self, w: torch.Tensor, b: Optional[torch.Tensor]):
+        gw, acc = self.slot(w)
+        return gw, (self.slot(b)[0] if b is not None else None), acc
+
+    def conv3x3(self, w, b, x: torch.Tensor, gy: torch.Tensor, **kw) -> None:
+        """ops.conv3x3_wgrad; kw: ups, bias_n, defer."""
+        gw, gb, acc = self._slots(w, b)
+        ops.conv3x3_wgrad(x, gy, gw, gb, accumulate=acc, **kw)
+
+    def conv1x1(self, w, b, x: torch.Tensor, gy: torch.Tensor, **kw) -> None:
+        """ops.conv1x1_wgrad; kw: tanh_y, bias_n."""
+        gw, gb, acc = self._slots(w, b)
+        ops.conv1x1_wgrad(x, gy, gw, gb, accumulate=acc, **kw)
+
+    def linear(self, w, b, x: torch.Tensor, gy: torch.Tensor, **kw):
+        """ops.linear1_bwd of the classifier -> its data gradient (None with need_gx=False); kw: need_gx, bias_n."""
+        gw, gb, acc = self._slots(w, b)
+        return ops.linear1_bwd(x, w, gy, gw=gw, gb=gb, accumulate=acc, **kw)
+
+    def gen_head(self, w, b, g_mp: torch.Tensor, mp: torch.Tensor, p: torch.Tensor, rn: torch.Tensor, **kw) -> torch.Tensor:
+        """ops.gen_head_bwd: a generator head's weight and bias gradient -> the masked gradient in front of the PixelNorm; kw: g_in."""
+        gw, gb, acc = self._slots(w, b)
+        return ops.gen_head_bwd(g_mp, mp, w, p, rn, gw, gb, accumulate=acc, **kw)
+
 
 # =====================================================================================================================
 # Generator
@@ -341,18 +373,42 @@ class GenWeights:
         return out
 
 
+class GenBlock(NamedTuple):
+    """What a generator block keeps for its backward pass: its input, and of both convs only the normalised output p and the
+    per-pixel 1 / norm (the backward derives mask and x_hat from p)."""
+    xin: torch.Tensor
+    rn1: torch.Tensor
+    p1: torch.Tensor
+    rn2: torch.Tensor
+    p2: torch.Tensor
+
+
+class GenCtx(NamedTuple):
+    """gen_forward(save=True) -> gen_backward.  `head_chain` is a route the backward pass follows, not one it decides again."""
+    saved: List[GenBlock]
+    x: torch.Tensor               # the last block's output p2: what the head reads
+    mp: torch.Tensor              # the head's output
+    old: Optional[torch.Tensor]   # the old head's output while it fades out
+    alpha: object                 # float or FadeIn
+    head_chain: bool              # the first three convs ran as one SmallNet launch (gen_head_ok at the time of the forward pass)
+
+
 def gen_forward(W: GenWeights, z: torch.Tensor, alpha: float, cache: PackCache, save: bool, out=None):
     x = z.contiguous()
-    saved = []
     # the 1x1 head in the last conv's epilogue where that conv is the 9-component up-sampling kernel: [hw, hb, mp buffer, result]
     head_req = [W.head[0], W.head[1], out if W.old_head is None else None, None] if W.head[0].shape[0] == 2 else None
-    head = gen_head_ok(W, x)
-    if head:
+    convs = []
+    for (w1, b1, w2, b2) in W.blocks:
+        convs += [(w1, b1, w1.shape[0], False), (w2, b2, w2.shape[0], True)]
+    pr = [None] * len(convs)    # (p, rn) per conv
+    head_chain = gen_head_ok(W, x)
+    if head_chain:
         # block 0 and the first conv of block 1 in one launch (activations in LDS); only what the backward pass needs is stored
         n, rc = x.shape[0], x.shape[1]
         (w1a, b1a, w2a, b2a), (w1b, b1b, _, _) = W.blocks[0], W.blocks[1]
         c0, c1 = w2a.shape[0], w1b.shape[0]
         new = lambda c, s: torch.empty((n, c, s, s), dtype=torch.float32, device=x.device)
+        # (without `save` p2a stays None: the old head reads the LAST block's input, and gen_head_ok wants three blocks)
         p1a, rn1a, p2a, rn2a = (new(rc, 2), new(1, 2), new(c0, 4), new(1, 4)) if save else (None,) * 4
         p1b, rn1b = new(c1, 4), (new(1, 4) if save else None)
         sn = ops.SmallNet(_imgs_per_wg(n))
@@ -362,63 +418,40 @@ def gen_forward(W: GenWeights, z: torch.Tensor, alpha: float, cache: PackCache, 
         sn.conv(2, 0, cache.get_sn(w2a, False), rc, c0, 4, 4, bias=b2a, lrelu=True).pixnorm(0, c0, 4, 4, p2a, rn2a)
         sn.conv(0, 1, cache.get_sn(w1b, False), c0, c1, 4, 4, bias=b1b, lrelu=True).pixnorm(1, c1, 4, 4, p1b, rn1b)
         sn.run(n)
-    if not head and os.environ.get("MG_PN_STAGED", "1") != "0":
-        # PixelNorm folded into the NEXT convolution's input staging wherever both neighbours are small-map launches: a conv leaves
-        # its LeakyReLU output un-normalised ("raw") and the following mg_conv3x3_small_pn normalises while staging, writing p and
-        # 1 / norm as side outputs -- four PixelNorm launches fewer per generator forward pass from level 3 on.
-        convs = []
-        for (w1, b1, w2, b2) in W.blocks:
-            convs += [(w1, b1, w1.shape[0], False), (w2, b2, w2.shape[0], True)]
-        cur, raw = x, None          # the normalised input of the next conv, or (raw) an activation whose PixelNorm is pending
-        pr = [None] * len(convs)    # (p, rn) per conv
-        for k, (w, b, cout, ups) in enumerate(convs):
-            if raw is not None:
-                probe = raw
-                if PackCache.small_ok(probe, cout, ups=ups, lrelu=True):
-                    # (without `save` only the input of the last block is still needed as a tensor: the old head reads it)
-                    need = save or (W.old_head is not None and k - 1 == len(convs) - 3)
-                    y, p_prev, rn_prev = ops.conv3x3_small_pn(raw, cache.get_sn(w, False), b, cout, ups=ups, save=need)
-                    pr[k - 1] = (p_prev, rn_prev)
-                    raw = y
-                    continue
-                cur, rn_prev = ops.pixelnorm_fwd(raw)
-                pr[k - 1] = (cur, rn_prev)
-                raw = None
-            n_, ci_, h_, w_ = cur.shape
-            if gen_conv_form(n_, ci_, cout, h_, w_, ups) == "conv+pixnorm" and PackCache.small_ok(cur, cout, ups=ups, lrelu=True):
-                raw = cache.conv(cur, w, False, b, cout, ups=ups, lrelu=True)  # its PixelNorm: by the next conv, or below
-            else:
-                cur, rn_k = cache.conv_lrelu_pixnorm(cur, w, b, cout, ups=ups, head=head_req if k == len(convs) - 1 else None)
-                pr[k] = (cur, rn_k)
+        pr[:3] = (p1a, rn1a), (p2a, rn2a), (p1b, rn1b)
+    # PixelNorm folded into the NEXT convolution's input staging wherever both neighbours are small-map launches: a conv leaves
+    # its LeakyReLU output un-normalised ("raw") and the following mg_conv3x3_small_pn normalises while staging, writing p and
+    # 1 / norm as side outputs -- four PixelNorm launches fewer per generator forward pass from level 3 on.
+    staged = not head_chain and os.environ.get("MG_PN_STAGED", "1") != "0"
+    # the normalised input of the next conv, or (raw) an activation whose PixelNorm is pending
+    cur, raw = (pr[2][0] if head_chain else x), None
+    for k in range(3 if head_chain else 0, len(convs)):
+        w, b, cout, ups = convs[k]
         if raw is not None:
-            cur, rn_k = ops.pixelnorm_fwd(raw)
-            pr[-1] = (cur, rn_k)
-        xin = x
-        for bi in range(len(W.blocks)):
-            (p1, rn1), (p2, rn2) = pr[2 * bi], pr[2 * bi + 1]
-            if save:
-                saved.append((xin, rn1, p1, rn2, p2))
-            x_in_last, xin = xin, p2
-        x = xin
-        blocks_iter = ()
-    else:
-        blocks_iter = W.blocks
-    for bi, (w1, b1, w2, b2) in enumerate(blocks_iter):
-        ci, co = w1.shape[0], w2.shape[0]
-        if head and bi == 0:
-            if save:
-                saved.append((x, rn1a, p1a, rn2a, p2a))
-            x_in_last, x = x, p2a
-            continue
-        # only the normalised outputs p and the per-pixel 1/norm are kept: the backward derives mask and x_hat from p
-        if head and bi == 1:
-            p1, rn1 = p1b, rn1b
+            if PackCache.small_ok(raw, cout, ups=ups, lrelu=True):
+                # (without `save` only the input of the last block is still needed as a tensor: the old head reads it)
+                need = save or (W.old_head is not None and k - 1 == len(convs) - 3)
+                raw, p_prev, rn_prev = ops.conv3x3_small_pn(raw, cache.get_sn(w, False), b, cout, ups=ups, save=need)
+                pr[k - 1] = (p_prev, rn_prev)
+                continue
+            pr[k - 1] = ops.pixelnorm_fwd(raw)
+            cur, raw = pr[k - 1][0], None
+        n_, ci_, h_, w_ = cur.shape
+        if staged and gen_conv_form(n_, ci_, cout, h_, w_, ups) == "conv+pixnorm" and PackCache.small_ok(cur, cout, ups=ups, lrelu=True):
+            raw = cache.conv(cur, w, False, b, cout, ups=ups, lrelu=True)  # its PixelNorm: by the next conv, or below
         else:
-            p1, rn1 = cache.conv_lrelu_pixnorm(x, w1, b1, ci)
-        p2, rn2 = cache.conv_lrelu_pixnorm(p1, w2, b2, co, ups=True, head=head_req if bi == len(W.blocks) - 1 else None)
+            pr[k] = cache.conv_lrelu_pixnorm(cur, w, b, cout, ups=ups, head=head_req if k == len(convs) - 1 else None)
+            cur = pr[k][0]
+    if raw is not None:
+        pr[-1] = ops.pixelnorm_fwd(raw)
+    saved = []
+    xin = x
+    for bi in range(len(W.blocks)):
+        (p1, rn1), (p2, rn2) = pr[2 * bi], pr[2 * bi + 1]
         if save:
-            saved.append((x, rn1, p1, rn2, p2))
-        x_in_last, x = x, p2
+            saved.append(GenBlock(xin, rn1, p1, rn2, p2))
+        x_in_last, xin = xin, p2
+    x = xin
     old = None
     mp_epi = head_req[3] if head_req is not None else None
     if mp_epi is not None and W.old_head is None:
@@ -439,15 +472,14 @@ def gen_forward(W: GenWeights, z: torch.Tensor, alpha: float, cache: PackCache, 
             out = ops.blend_up(F.a, mp, F.b, old, out=out, coef=F.dev)
     else:
         out = mp = ops.conv1x1(x, W.head[0], W.head[1], 2, tanh=True, out=out)
-    ctx = (saved, x, mp, old, alpha) if save else None
-    return out, ctx
+    return out, (GenCtx(saved, x, mp, old, alpha, head_chain) if save else None)
 
 
-def gen_backward(W: GenWeights, ctx, g_out: torch.Tensor, cache: PackCache, sink: GradSink, need_gz: bool = False,
+def gen_backward(W: GenWeights, ctx: GenCtx, g_out: torch.Tensor, cache: PackCache, sink: GradSink, need_gz: bool = False,
                  defer: Optional["ops.WgradDefer"] = None):
     """`defer`: the Winograd weight-gradient reductions are collected there; the caller flushes it (one launch for all layers)."""
-    saved, x_last, mp, old, alpha = ctx
-    F = FadeIn.of(alpha)
+    saved, x_last, mp, old = ctx.saved, ctx.x, ctx.mp, ctx.old
+    F = FadeIn.of(ctx.alpha)
     g_out = g_out.contiguous()
     if W.old_head is not None and ops.blend_up_bwd_supported(g_out.shape[2], g_out.shape[3]):
         g_mp, g_old = ops.blend_up_bwd(g_out, F.a, F.b, coef=F.dev)
@@ -457,38 +489,33 @@ def gen_backward(W: GenWeights, ctx, g_out: torch.Tensor, cache: PackCache, sink
         g_old = ops.axpby(F.b, g_old, out=g_old, coef=F.dev_b)
     else:
         g_mp, g_old = g_out, None
-    gw, acc = sink.slot(W.head[0])
-    gb, _ = sink.slot(W.head[1])
     last = len(W.blocks) - 1
     gpre_head = None
     if ops.gen_head_bwd_supported(x_last.shape[1], W.head[0].shape[0], x_last.shape[0], x_last.shape[2] * x_last.shape[3]) \
-            and saved[last][4] is x_last:
+            and saved[last].p2 is x_last:
         # the head's weight gradient, its data gradient and the PixelNorm / LeakyReLU backward of the last conv: one pass over p
-        gpre_head = ops.gen_head_bwd(g_mp, mp, W.head[0], x_last, saved[last][3], gw, gb, accumulate=acc)
+        gpre_head = sink.gen_head(W.head[0], W.head[1], g_mp, mp, x_last, saved[last].rn2)
         g = None
     else:
-        ops.conv1x1_wgrad(x_last, g_mp, gw, gb, tanh_y=mp, accumulate=acc)
+        sink.conv1x1(W.head[0], W.head[1], x_last, g_mp, tanh_y=mp)
         g = ops.conv1x1(g_mp, W.head[0], None, x_last.shape[1], transposed=True, tanh_bwd_in=mp)
     gz = None
-    old_pending = None
+    old_pending = False
     for i in range(last, -1, -1):
         w1, b1, w2, b2 = W.blocks[i]
-        xin, rn1, p1, rn2, p2 = saved[i]
+        blk = saved[i]
+        xin, p1, rn1 = blk.xin, blk.p1, blk.rn1
         ci = w1.shape[0]
         if i == last and gpre_head is not None:
             gpre2 = gpre_head
-        elif old_pending is not None:
+        elif old_pending:
             # the old head's weight / data gradient joins the conv's data gradient g inside the PixelNorm backward's pass over p2
-            gwo, acc = sink.slot(W.old_head[0])
-            gbo, _ = sink.slot(W.old_head[1])
-            gpre2 = ops.gen_head_bwd(g_old, old, W.old_head[0], p2, rn2, gwo, gbo, accumulate=acc, g_in=g)
-            old_pending = None
+            gpre2 = sink.gen_head(W.old_head[0], W.old_head[1], g_old, old, blk.p2, blk.rn2, g_in=g)
+            old_pending = False
         else:
-            gpre2 = ops.pixelnorm_lrelu_bwd(g, p2, rn2, from_p=True)
-        gw2, acc = sink.slot(w2)
-        gb2, _ = sink.slot(b2)
-        ops.conv3x3_wgrad(p1, gpre2, gw2, gb2, ups=True, accumulate=acc, defer=defer)
-        small_tail = i == 1 and gen_head_ok(W, saved[0][0])
+            gpre2 = ops.pixelnorm_lrelu_bwd(g, blk.p2, blk.rn2, from_p=True)
+        sink.conv3x3(w2, b2, p1, gpre2, ups=True, defer=defer)
+        small_tail = i == 1 and ctx.head_chain
         gpre1 = None
         if ops.winoups3x3_supported(p1.shape[0], ci, w2.shape[0], p1.shape[2], p1.shape[3], dgrad=True):
             if not small_tail and ops.winoups3x3_dgrad_pn_supported(p1.shape[0], ci, w2.shape[0], p1.shape[2], p1.shape[3]):
@@ -503,7 +530,8 @@ def gen_backward(W: GenWeights, ctx, g_out: torch.Tensor, cache: PackCache, sink
         if small_tail:
             # the data-gradient chain of the generator's first three convs in one launch; their weight gradients from the
             # stored masked gradients
-            z, rn1a, p1a, rn2a, p2a = saved[0]
+            b0 = saved[0]
+            z = b0.xin
             w1a, b1a, w2a, b2a = W.blocks[0]
             n, rc, c0 = z.shape[0], z.shape[1], w2a.shape[0]
             new = lambda c, s: torch.empty((n, c, s, s), dtype=torch.float32, device=z.device)
@@ -513,33 +541,28 @@ def gen_backward(W: GenWeights, ctx, g_out: torch.Tensor, cache: PackCache, sink
             sn.load(0, gp1)
             sn.pnbwd(0, ci, 4, 4, p1, rn1, out=gpre1)
             sn.conv(0, 1, cache.get_sn(w1, True), ci, c0, 4, 4)
-            sn.pnbwd(1, c0, 4, 4, p2a, rn2a, out=gpre2a)
+            sn.pnbwd(1, c0, 4, 4, b0.p2, b0.rn2, out=gpre2a)
             sn.conv(1, 2, cache.get_sn(w2a, True), c0, rc, 4, 4)
             sn.upbwd(2, 0, rc, 4, 4)
-            sn.pnbwd(0, rc, 2, 2, p1a, rn1a, out=gpre1a)
+            sn.pnbwd(0, rc, 2, 2, b0.p1, b0.rn1, out=gpre1a)
             if need_gz:
                 sn.conv(0, 1, cache.get_sn(w1a, True), rc, rc, 2, 2, out=gz)
             sn.run(n)
-            for wt, bt, xi, gy, ups in ((w1, b1, xin, gpre1, False), (w2a, b2a, p1a, gpre2a, True), (w1a, b1a, z, gpre1a, False)):
-                gwt, acc = sink.slot(wt)
-                gbt, _ = sink.slot(bt)
-                ops.conv3x3_wgrad(xi, gy, gwt, gbt, ups=ups, accumulate=acc, defer=defer)
+            sink.conv3x3(w1, b1, xin, gpre1, ups=False, defer=defer)
+            sink.conv3x3(w2a, b2a, b0.p1, gpre2a, ups=True, defer=defer)
+            sink.conv3x3(w1a, b1a, z, gpre1a, ups=False, defer=defer)
             break
         if gpre1 is None:
             gpre1 = ops.pixelnorm_lrelu_bwd(gp1, p1, rn1, from_p=True)
-        gw1, acc = sink.slot(w1)
-        gb1, _ = sink.slot(b1)
-        ops.conv3x3_wgrad(xin, gpre1, gw1, gb1, accumulate=acc, defer=defer)
+        sink.conv3x3(w1, b1, xin, gpre1, defer=defer)
         if i > 0:
             g = cache.conv(gpre1, w1, True, None, ci)
             if g_old is not None and i == last and ops.gen_head_bwd_supported(xin.shape[1], W.old_head[0].shape[0], xin.shape[0],
                                                                               xin.shape[2] * xin.shape[3]) \
-                    and saved[last - 1][4] is xin:
+                    and saved[last - 1].p2 is xin:
                 old_pending = True  # (handled at the top of the next turn)
             elif g_old is not None and i == last:
-                gwo, acc = sink.slot(W.old_head[0])
-                gbo, _ = sink.slot(W.old_head[1])
-                ops.conv1x1_wgrad(xin, g_old, gwo, gbo, tanh_y=old, accumulate=acc)
+                sink.conv1x1(W.old_head[0], W.old_head[1], xin, g_old, tanh_y=old)
                 if ops.fuse_ends():  # the old head's branch joins in the conv's epilogue
                     ops.conv1x1(g_old, W.old_head[0], None, xin.shape[1], transposed=True, tanh_bwd_in=old, out=g, accumulate=True)
                 else:
@@ -570,10 +593,50 @@ class DiscWeights:
         return out
 
 
+class DiscBlock(NamedTuple):
+    """What a critic block keeps: its input, the first conv's activation, the pooled activation, the second conv's activation.
+    `a1` and `a2` are EITHER the fp32 activation OR, where a later pass only needs its sign, a uint8 tile mask (one byte per 2x2
+    tile, (N, C, H/2, W/2)).  disc_forward alone decides which -- `_tile_mask_ok` for a1, `_fade_fused_ok` for the a2 of the
+    fade-in block -- and every later pass branches on the dtype it finds, never on the switches again.  The in-place tangent pass
+    of disc_step_fused overwrites the interpolated rows of the fp32 ones with the tangent."""
+    inp: torch.Tensor
+    a1: torch.Tensor
+    q1: torch.Tensor
+    a2: torch.Tensor
+
+    def rows(self, sl: slice) -> "DiscBlock":
+        """The same record over a slice of the batch (views)."""
+        return DiscBlock(*(u[sl] for u in self))
+
+
+class DiscCtx(NamedTuple):
+    """disc_forward(save=True) -> disc_backward, disc_gp_param_grads and the tangent pass of disc_step_fused.  `tail` and
+    `fused_stem` are routes those passes follow, not ones they decide again: the saved tensors have the layout of that route."""
+    x: torch.Tensor
+    h0: torch.Tensor                # the stem's activation
+    saved: List[DiscBlock]
+    xp: Optional[torch.Tensor]      # AvgPool2d(x), the old stem's input (fade-in only)
+    o: Optional[torch.Tensor]       # the old stem's activation
+    flat: torch.Tensor              # the classifier's input (N, 160)
+    alpha: object                   # float or FadeIn
+    h0m: Optional[torch.Tensor]     # uint8 tile mask of h0 where the stem wrote one
+    tail: Optional[int]             # disc_tail_start at the time of the forward pass: the SmallNet tail begins in that block
+    fused_stem: bool                # both stems and the pooled input came from one ops.stem_pair launch
+
+
+@dataclass
+class MaskedGrads:
+    """The masked per-layer gradients h_l of a backward pass (keep_h), which the penalty's second-order pass multiplies with its
+    tangents: per block (gpre1, gpre2) in front of its two convs, and those in front of the stem and the old stem."""
+    blocks: List[Optional[Tuple[torch.Tensor, torch.Tensor]]]
+    stem: Optional[torch.Tensor] = None
+    old: Optional[torch.Tensor] = None
+
+
 def _tile_mask_ok(n: int, cin: int, cout: int, h: int, w: int) -> bool:
     """Tile masks are an epilogue of the Winograd kernel: usable where it runs for the whole batch AND for the third of it that
     the penalty's tangent pass sends through the same layer again (MG_TILEMASK=0 keeps fp32 activations everywhere)."""
-    if os.environ.get("MG_TILEMASK", "1") == "0" or (w % 4) or (h % 2):
+    if not _tilemask_on() or (w % 4) or (h % 2):
         return False
     if h <= 8 and w <= 8 and _smallnet_on():
         return False  # the fused tail's un-pooling step reads the fp32 activation of the 8x8 layer
@@ -583,7 +646,7 @@ def _tile_mask_ok(n: int, cin: int, cout: int, h: int, w: int) -> bool:
 def _fade_fused_ok(n: int, c1: int, c_next: int, h: int, w: int) -> bool:
     """Whether the fade-in blend rides on the Winograd convs around it (ops.conv3x3_fade): the block's second conv forward and
     in the tangent pass (a third of the batch), and the data-gradient conv of the next block's first conv on the way back."""
-    if os.environ.get("MG_TILEMASK", "1") == "0" or c_next == 0 or (w % 4) or (h % 2):
+    if not _tilemask_on() or c_next == 0 or (w % 4) or (h % 2):
         return False
     nmin = max(1, n // 3)
     return ops.wino3x3_supported(nmin, c1, h, w, cin=c1) and ops.wino3x3_supported(nmin, c1, h, w, cin=c_next)
@@ -591,10 +654,10 @@ def _fade_fused_ok(n: int, c1: int, c_next: int, h: int, w: int) -> bool:
 
 def _disc_tail_forward(W: DiscWeights, t: int, q1: torch.Tensor, cache: PackCache, save: bool, masks=None):
     """conv2 of block t (4x4), blocks t+1 (4x4 -> 2x2) and t+2 (2x2 -> 1x1) and the classifier in one launch.  Returns (scores,
-    [(a2_t,), (inp, a1, q1, a2) of block t+1, ... of block t+2]) -- the tuples only with `save`.
-    `masks` (the tangent pass of the penalty): the saved tuples of a forward pass; every conv is then bias-free, multiplied by
-    the LeakyReLU derivative of the saved activation, and written over it (q1 must be the tangent of block t's pooled output, in
-    place in the saved tensor); nothing is returned."""
+    a2 of block t, [DiscBlock of block t+1, of block t+2]) -- a2 and the records' tensors only with `save`.
+    `masks` (the tangent pass of the penalty): the saved records of blocks t .. t+2 of a forward pass; every conv is then
+    bias-free, multiplied by the LeakyReLU derivative of the saved activation, and written over it (q1 must be the tangent of
+    block t's pooled output, in place in the saved tensor); nothing is returned."""
     n = q1.shape[0]
     dev = q1.device
     tangent = masks is not None
@@ -605,25 +668,25 @@ def _disc_tail_forward(W: DiscWeights, t: int, q1: torch.Tensor, cache: PackCach
     sn.load(0, q1)
     cur = 0
     rest = []
-    a2 = masks[0][3] if tangent else (new(c1, 4) if save else None)
+    a2_t = a2 = masks[0].a2 if tangent else (new(c1, 4) if save else None)
     nxt = _rot(cur)[0]
     sn.conv(cur, nxt, cache.get_sn(w2, False), c1, c1, 4, 4, bias=None if tangent else b2, lrelu=not tangent,
             mask=a2 if tangent else None, out=a2)
-    rest.append((a2,))
     cur, cin, h, inp = nxt, c1, 4, a2
     for k, j in enumerate((t + 1, t + 2)):
         w1, b1, w2, b2 = W.blocks[j]
         c1 = w1.shape[0]
-        a1 = masks[k + 1][1] if tangent else (new(c1, h) if save else None)
-        qn = masks[k + 1][2] if tangent else (new(c1, h // 2) if save else None)
-        a2 = masks[k + 1][3] if tangent else (new(c1, h // 2) if save else None)
+        if tangent:
+            a1, qn, a2 = masks[k + 1].a1, masks[k + 1].q1, masks[k + 1].a2
+        else:
+            a1, qn, a2 = (new(c1, h), new(c1, h // 2), new(c1, h // 2)) if save else (None,) * 3
         b_a, b_q = _rot(cur)
         sn.conv(cur, b_a, cache.get_sn(w1, False), cin, c1, h, h, bias=None if tangent else b1, lrelu=not tangent,
                 mask=a1 if tangent else None, out=a1)
         sn.pool(b_a, b_q, c1, h, h, out=qn)
         sn.conv(b_q, cur, cache.get_sn(w2, False), c1, c1, h // 2, h // 2, bias=None if tangent else b2, lrelu=not tangent,
                 mask=a2 if tangent else None, out=a2)
-        rest.append((inp, a1, qn, a2))
+        rest.append(DiscBlock(inp, a1, qn, a2))
         cin, h, inp = c1, h // 2, a2
     if tangent:
         sn.run(n)
@@ -631,7 +694,7 @@ def _disc_tail_forward(W: DiscWeights, t: int, q1: torch.Tensor, cache: PackCach
     out = torch.empty((n, 1), dtype=torch.float32, device=dev)
     sn.linear(cur, cin, W.clf[0], W.clf[1], out)
     sn.run(n)
-    return out, rest
+    return out, a2_t, rest
 
 
 def _disc_tail_backward(W: DiscWeights, t: int, saved, g_out: torch.Tensor, cache: PackCache):
@@ -647,27 +710,25 @@ def _disc_tail_backward(W: DiscWeights, t: int, saved, g_out: torch.Tensor, cach
     c_last = W.blocks[last][0].shape[0]
     gpre2 = new(c_last, 1)
     sn.linbwd(0, c_last, g_out, W.clf[0])
-    sn.mask(0, c_last, 1, 1, saved[last][3], out=gpre2)
+    sn.mask(0, c_last, 1, 1, saved[last].a2, out=gpre2)
     cur, h = 0, 1
     for j in (last, last - 1):
         w1, b1, w2, b2 = W.blocks[j]
         c1, cin = w1.shape[0], w1.shape[1]
-        inp, a1, q1, a2 = saved[j]
         gpre1 = new(c1, 2 * h)
         gprev = new(cin, 2 * h)   # masked gradient behind the previous block's second conv
         b_a, b_b = _rot(cur)
         sn.conv(cur, b_a, cache.get_sn(w2, True), c1, c1, h, h)
-        sn.poolbwd(b_a, b_b, c1, h, h, a1, out=gpre1)
-        sn.conv(b_b, cur, cache.get_sn(w1, True), c1, cin, 2 * h, 2 * h, mask=saved[j - 1][3], out=gprev)
+        sn.poolbwd(b_a, b_b, c1, h, h, saved[j].a1, out=gpre1)
+        sn.conv(b_b, cur, cache.get_sn(w1, True), c1, cin, 2 * h, 2 * h, mask=saved[j - 1].a2, out=gprev)
         hs[j] = (gpre1, gpre2)
         gpre2, h = gprev, 2 * h
     w1, b1, w2, b2 = W.blocks[t]
     c1 = w1.shape[0]
-    inp, a1, q1, a2 = saved[t]
     gpre1 = new(c1, 8)
     b_a, b_b = _rot(cur)
     sn.conv(cur, b_a, cache.get_sn(w2, True), c1, c1, 4, 4)
-    sn.poolbwd(b_a, b_b, c1, 4, 4, a1, out=gpre1, lds=False)
+    sn.poolbwd(b_a, b_b, c1, 4, 4, saved[t].a1, out=gpre1, lds=False)
     hs[t] = (gpre1, gpre2)
     sn.run(n)
     return hs
@@ -677,14 +738,13 @@ def disc_forward(W: DiscWeights, x: torch.Tensor, alpha: float, cache: PackCache
     x = x.contiguous()
     n = x.shape[0]
     c0 = W.stem[0].shape[0]
-    xp = o = None
+    xp = o = h0m = None
     fused_stem = W.old_stem is not None and ops.stem_pair_supported(x.shape[2], x.shape[3])
-    h0m = None
     if fused_stem:  # the new block's stem, the pooled input and the old block's stem on it: one pass over x
         # of h0 the data-gradient conv in front of the stem only needs the sign: where that conv is the Winograd kernel the stem also
         # leaves one byte per 2x2 tile and channel, 1/16 of the bytes the fp32 mask costs that launch (the largest of a D / G backward)
         c1_0 = W.blocks[0][0].shape[0]
-        if save and os.environ.get("MG_TILEMASK", "1") != "0" and os.environ.get("MG_STEM_TILEMASK", "1") != "0" and \
+        if save and _tilemask_on() and os.environ.get("MG_STEM_TILEMASK", "1") != "0" and \
                 ops.wino3x3_supported(n, c0, x.shape[2], x.shape[3], cin=c1_0) and \
                 ops.wino3x3_mask_bytes_y_supported(n, c1_0, c0, x.shape[2], x.shape[3]):
             h0, xp, o, h0m = ops.stem_pair(x, W.stem[0], W.stem[1], W.old_stem[0], W.old_stem[1], want_xp=save, want_mask=True)
@@ -697,16 +757,15 @@ def disc_forward(W: DiscWeights, x: torch.Tensor, alpha: float, cache: PackCache
     tail = disc_tail_start(W, x.shape[2], x.shape[3])
     for i, (w1, b1, w2, b2) in enumerate(W.blocks):
         c1 = w1.shape[0]
-        if tail is not None and i == tail:
+        if i == tail:
             # this block's first conv (8x8) on its own, then everything behind it -- its second conv, the two last blocks and the
             # classifier -- as ONE launch with the activations in LDS; the tensors the backward passes read are stored on the way
             a1, q1 = cache.conv(inp, w1, False, b1, c1, lrelu=True, pool=True)
-            out, rest = _disc_tail_forward(W, tail, q1, cache, save)
+            out, a2, rest = _disc_tail_forward(W, tail, q1, cache, save)
             if save:
-                saved.append((inp, a1, q1, rest[0][0]))
-                saved.extend(rest[1:])
-            flat = rest[-1][3].reshape(n, -1) if save else None
-            return out, ((x, h0, saved, xp, o, flat, alpha, h0m) if save else None)
+                saved += [DiscBlock(inp, a1, q1, a2)] + rest
+                flat = rest[-1].a2.reshape(n, -1)
+            break
         # AvgPool2d fused in the epilogue.  Of the full-resolution activation the backward passes only need the sign, so on the
         # large maps (Winograd kernel, for every batch slice that will come back with the mask) it is kept as one byte per
         # 2x2 tile and a1 is that uint8 tile mask (N,c1,H/2,W/2) instead of the fp32 tensor.
@@ -727,56 +786,47 @@ def disc_forward(W: DiscWeights, x: torch.Tensor, alpha: float, cache: PackCache
         else:
             a2 = nxt = cache.conv(q1, w2, False, b2, c1, lrelu=True)
         if save:
-            saved.append((inp, a1, q1, a2))
+            saved.append(DiscBlock(inp, a1, q1, a2))
         inp = nxt
-    assert inp.shape[2] == 1 and inp.shape[3] == 1, \
-        f"discriminator input must be square with side 2**(9-curr_layer); final map is {tuple(inp.shape)}"
-    flat = inp.reshape(n, -1)
-    out = ops.linear1_fwd(flat, W.clf[0], W.clf[1])
-    ctx = (x, h0, saved, xp, o, flat, alpha, h0m) if save else None
-    return out, ctx
+    if tail is None:
+        assert inp.shape[2] == 1 and inp.shape[3] == 1, \
+            f"discriminator input must be square with side 2**(9-curr_layer); final map is {tuple(inp.shape)}"
+        flat = inp.reshape(n, -1)
+        out = ops.linear1_fwd(flat, W.clf[0], W.clf[1])
+    return out, (DiscCtx(x, h0, saved, xp, o, flat, alpha, h0m, tail, fused_stem) if save else None)
 
 
-def disc_backward(W: DiscWeights, ctx, g_out: torch.Tensor, cache: PackCache, sink: Optional[GradSink],
+def disc_backward(W: DiscWeights, ctx: DiscCtx, g_out: torch.Tensor, cache: PackCache, sink: Optional[GradSink],
                   need_gx: bool, keep_h: bool = False, gx_from: int = 0):
     """Back-propagate g_out (N,1).  sink=None skips all parameter gradients (first-order pass of the penalty).
-    keep_h returns the masked per-layer gradients h_l needed by disc_gp_param_grads()."""
-    x, h0, saved, xp, o, flat, alpha, h0m = ctx
-    F = FadeIn.of(alpha)
+    keep_h returns the masked per-layer gradients h_l (MaskedGrads) needed by disc_gp_param_grads()."""
+    x, saved, o, tail = ctx.x, ctx.saved, ctx.o, ctx.tail
+    F = FadeIn.of(ctx.alpha)
     g_out = g_out.contiguous()
     n = x.shape[0]
     nb = len(W.blocks)
-    hs = {"blocks": [None] * nb, "stem": None, "old": None}
-    tail = disc_tail_start(W, x.shape[2], x.shape[3])
+    hs = MaskedGrads([None] * nb)
     gpre_o = gpre_s = None
     if tail is not None:
         # classifier + the <= 4x4 layers in one launch, down to the masked gradient in front of block `tail`'s first conv; their
         # weight gradients (if wanted) from the tensors it stored
         ths = _disc_tail_backward(W, tail, saved, g_out, cache)
         if sink is not None:
-            gwc, acc = sink.slot(W.clf[0])
-            gbc, _ = sink.slot(W.clf[1])
-            ops.linear1_bwd(flat, W.clf[0], g_out, gw=gwc, gb=gbc, need_gx=False, accumulate=acc)
+            sink.linear(W.clf[0], W.clf[1], ctx.flat, g_out, need_gx=False)
             for j in range(nb - 1, tail - 1, -1):
                 w1, b1, w2, b2 = W.blocks[j]
-                inp, a1, q1, a2 = saved[j]
-                gw2, acc = sink.slot(w2)
-                gb2, _ = sink.slot(b2)
-                ops.conv3x3_wgrad(q1, ths[j][1], gw2, gb2, accumulate=acc)
-                gw1, acc = sink.slot(w1)
-                gb1, _ = sink.slot(b1)
-                ops.conv3x3_wgrad(inp, ths[j][0], gw1, gb1, accumulate=acc)
+                h1, h2 = ths[j]
+                sink.conv3x3(w2, b2, saved[j].q1, h2)
+                sink.conv3x3(w1, b1, saved[j].inp, h1)
         for j in range(tail, nb):
-            hs["blocks"][j] = ths[j]
+            hs.blocks[j] = ths[j]
         first, gpre2 = tail, None
     else:
         if sink is not None:
-            gwc, acc = sink.slot(W.clf[0])
-            gbc, _ = sink.slot(W.clf[1])
-            g = ops.linear1_bwd(flat, W.clf[0], g_out, gw=gwc, gb=gbc, accumulate=acc)
+            g = sink.linear(W.clf[0], W.clf[1], ctx.flat, g_out)
         else:
-            g = ops.linear1_bwd(flat, W.clf[0], g_out, need_gx=True)
-        a2_last = saved[nb - 1][3]
+            g = ops.linear1_bwd(ctx.flat, W.clf[0], g_out, need_gx=True)
+        a2_last = saved[nb - 1].a2
         g = g.reshape(a2_last.shape)
         if nb == 1 and W.old_stem is not None:  # the blend is the classifier input
             gpre2, gpre_o = ops.blend_lrelu_bwd(g, a2_last, o, F.a, F.b, coef=F.dev)
@@ -785,27 +835,23 @@ def disc_backward(W: DiscWeights, ctx, g_out: torch.Tensor, cache: PackCache, si
         first = nb - 1
     for i in range(first, -1, -1):
         w1, b1, w2, b2 = W.blocks[i]
-        inp, a1, q1, a2 = saved[i]
+        blk = saved[i]
         c1, cin = w1.shape[0], w1.shape[1]
-        if tail is not None and i == tail:
-            gpre1 = hs["blocks"][i][0]
+        if i == tail:
+            gpre1 = hs.blocks[i][0]
         else:
             if sink is not None:
-                gw2, acc = sink.slot(w2)
-                gb2, _ = sink.slot(b2)
-                ops.conv3x3_wgrad(q1, gpre2, gw2, gb2, accumulate=acc)
-            if a1.dtype == torch.uint8 and ops.wino3x3_supported(n, c1, gpre2.shape[2], gpre2.shape[3], cin=c1):
-                gpre1 = cache.conv(gpre2, w2, True, None, c1, unpool_mask=a1)  # AvgPool2d + LeakyReLU backward in the conv epilogue
+                sink.conv3x3(w2, b2, blk.q1, gpre2)
+            if blk.a1.dtype == torch.uint8 and ops.wino3x3_supported(n, c1, gpre2.shape[2], gpre2.shape[3], cin=c1):
+                gpre1 = cache.conv(gpre2, w2, True, None, c1, unpool_mask=blk.a1)  # AvgPool2d + LeakyReLU backward in the conv epilogue
             else:
-                gpre1 = cache.conv_unpool(gpre2, w2, c1, a1)
+                gpre1 = cache.conv_unpool(gpre2, w2, c1, blk.a1)
             if sink is not None:
-                gw1, acc = sink.slot(w1)
-                gb1, _ = sink.slot(b1)
-                ops.conv3x3_wgrad(inp, gpre1, gw1, gb1, accumulate=acc)
-        if keep_h and hs["blocks"][i] is None:
-            hs["blocks"][i] = (gpre1, gpre2)
+                sink.conv3x3(w1, b1, blk.inp, gpre1)
+        if keep_h and hs.blocks[i] is None:
+            hs.blocks[i] = (gpre1, gpre2)
         if i > 0:
-            a2_prev = saved[i - 1][3]
+            a2_prev = saved[i - 1].a2
             if i == 1 and W.old_stem is not None:  # inp is the fade-in blend of a2_prev and the old stem path
                 if a2_prev.dtype == torch.uint8:  # blend + LeakyReLU backward in the data-gradient conv's epilogue
                     gpre2, gpre_o = ops.conv3x3_fade(gpre1, cache.get_wino(w1, True), None, cin, _lib.MG_FADE_BWD, o,
@@ -816,17 +862,13 @@ def disc_backward(W: DiscWeights, ctx, g_out: torch.Tensor, cache: PackCache, si
             else:
                 gpre2 = cache.conv(gpre1, w1, True, None, cin, mask_aux=a2_prev)
         else:
-            gpre_s = cache.conv(gpre1, w1, True, None, cin, mask_aux=h0m if h0m is not None else h0)
+            gpre_s = cache.conv(gpre1, w1, True, None, cin, mask_aux=ctx.h0m if ctx.h0m is not None else ctx.h0)
     if sink is not None:
-        gws, acc = sink.slot(W.stem[0])
-        gbs, _ = sink.slot(W.stem[1])
-        ops.conv1x1_wgrad(x, gpre_s, gws, gbs, accumulate=acc)
+        sink.conv1x1(W.stem[0], W.stem[1], x, gpre_s)
         if W.old_stem is not None:
-            gwo, acc = sink.slot(W.old_stem[0])
-            gbo, _ = sink.slot(W.old_stem[1])
-            ops.conv1x1_wgrad(xp, gpre_o, gwo, gbo, accumulate=acc)
+            sink.conv1x1(W.old_stem[0], W.old_stem[1], ctx.xp, gpre_o)
     if keep_h:
-        hs["stem"], hs["old"] = gpre_s, gpre_o
+        hs.stem, hs.old = gpre_s, gpre_o
     gx = None
     if need_gx and W.old_stem is not None and ops.stem_pair_gx_supported(gpre_s.shape[1], gpre_o.shape[1], x.shape[2], x.shape[3]):
         gx = ops.stem_pair_gx(gpre_s[gx_from:], W.stem[0], gpre_o[gx_from:], W.old_stem[0])  # both branches and their sum, one launch
@@ -838,43 +880,38 @@ def disc_backward(W: DiscWeights, ctx, g_out: torch.Tensor, cache: PackCache, si
     return gx, (hs if keep_h else None)
 
 
-def disc_gp_param_grads(W: DiscWeights, ctx, hs, u0: torch.Tensor, cache: PackCache, sink: GradSink,
+def disc_gp_param_grads(W: DiscWeights, ctx: DiscCtx, hs: MaskedGrads, u0: torch.Tensor, cache: PackCache, sink: GradSink,
                         g_out: Optional[torch.Tensor] = None, want_t: bool = False):
     """Second-order pass of the gradient penalty: tangent-forward u_l = mask_l * L_l u_{l-1} and dP/dW_l = wgrad(u_{l-1}, h_l).
     Biases receive no gradient from the penalty."""
-    x, h0, saved, xp, o, flat, alpha, _ = ctx
+    x = ctx.x
     n = x.shape[0]
     c0 = W.stem[0].shape[0]
-    gws, acc = sink.slot(W.stem[0])
-    ops.conv1x1_wgrad(u0, hs["stem"], gws, None, accumulate=acc)
-    t = ops.conv1x1(u0, W.stem[0], None, c0, mask_aux=h0)
+    sink.conv1x1(W.stem[0], None, u0, hs.stem)
+    t = ops.conv1x1(u0, W.stem[0], None, c0, mask_aux=ctx.h0)
     to = None
     if W.old_stem is not None:
         u0p = ops.avgpool2_fwd(u0)
-        gwo, acc = sink.slot(W.old_stem[0])
-        ops.conv1x1_wgrad(u0p, hs["old"], gwo, None, accumulate=acc)
-        to = ops.conv1x1(u0p, W.old_stem[0], None, W.old_stem[0].shape[0], mask_aux=o)
+        sink.conv1x1(W.old_stem[0], None, u0p, hs.old)
+        to = ops.conv1x1(u0p, W.old_stem[0], None, W.old_stem[0].shape[0], mask_aux=ctx.o)
     for i, (w1, b1, w2, b2) in enumerate(W.blocks):
-        inp, a1, q1, a2 = saved[i]
-        gpre1, gpre2 = hs["blocks"][i]
+        a1, a2 = ctx.saved[i].a1, ctx.saved[i].a2
+        gpre1, gpre2 = hs.blocks[i]
         c1 = w1.shape[0]
-        gw1, acc = sink.slot(w1)
-        ops.conv3x3_wgrad(t, gpre1, gw1, None, accumulate=acc)
+        sink.conv3x3(w1, None, t, gpre1)
         t1, tq = cache.conv(t, w1, False, None, c1, mask_aux=a1, pool=True)
-        gw2, acc = sink.slot(w2)
-        ops.conv3x3_wgrad(tq, gpre2, gw2, None, accumulate=acc)
+        sink.conv3x3(w2, None, tq, gpre2)
         if a2.dtype == torch.uint8:
-            F = FadeIn.of(alpha)
+            F = FadeIn.of(ctx.alpha)
             t = ops.conv3x3_fade(tq, cache.get_wino(w2, False), None, c1, _lib.MG_FADE_TANGENT, to, F.coef(x.device), mask_in=a2)
         else:
             t = cache.conv(tq, w2, False, None, c1, mask_aux=a2)
             if i == 0 and to is not None:
-                F = FadeIn.of(alpha)
+                F = FadeIn.of(ctx.alpha)
                 t = ops.axpby(F.a, t, F.b, to, out=t, coef=F.dev)
     # `g_out`: the upstream score gradient the first-order chain (hs) was run with -- ones for the penalty (discriminator.py:170-176)
     up = torch.ones((n, 1), dtype=torch.float32, device=x.device) if g_out is None else g_out.contiguous()
-    gwc, acc = sink.slot(W.clf[0])
-    ops.linear1_bwd(t.reshape(n, -1), W.clf[0], up, gw=gwc, gb=None, need_gx=False, accumulate=acc)
+    sink.linear(W.clf[0], None, t.reshape(n, -1), up, need_gx=False)
     if want_t:  # the tangent of the scores themselves, J(x) u0: the derivative w.r.t. the upstream score gradient
         zero = torch.zeros(1, dtype=torch.float32, device=x.device)
         return sink, ops.linear1_fwd(t.reshape(n, -1).contiguous(), W.clf[0], zero)
@@ -910,7 +947,7 @@ def disc_step_fused(W: DiscWeights, x_real: torch.Tensor, x_fake: torch.Tensor, 
     gx, hs = disc_backward(W, ctx, g_out, cache, None, need_gx=True, keep_h=True, gx_from=2 * n)  # input gradient: x~ only
     # penalty value and u_0 = dP/dg_0, written over the interpolated inputs (they are not needed any more)
     ss = ops.sumsq_per_sample(gx)
-    x, h0, saved, xp, o, flat, _, _ = ctx
+    x, h0, saved, xp, o = ctx.x, ctx.h0, ctx.saved, ctx.xp, ctx.o
     sl = slice(2 * n, 3 * n)
     if ops.fuse_ends():
         grad_pen, _ = ops.gp_apply(gx, ss, gp_factor, 1.0, out=x[sl])
@@ -919,7 +956,7 @@ def disc_step_fused(W: DiscWeights, x_real: torch.Tensor, x_fake: torch.Tensor, 
         ops.scale_per_sample(gx, coef, out=x[sl])
     # ---- tangent pass, in place over the interpolated slices
     c0 = W.stem[0].shape[0]
-    if W.old_stem is not None and ops.stem_pair_supported(x.shape[2], x.shape[3]):
+    if ctx.fused_stem:
         ops.stem_pair(x[sl], W.stem[0], None, W.old_stem[0], None, h0=h0[sl], xp=xp[sl], o=o[sl], masked=True)
     else:
         ops.conv1x1(x[sl], W.stem[0], None, c0, mask_aux=h0[sl], out=h0[sl])
@@ -927,48 +964,36 @@ def disc_step_fused(W: DiscWeights, x_real: torch.Tensor, x_fake: torch.Tensor, 
             ops.avgpool2_fwd(x[sl], out=xp[sl])
             ops.conv1x1(xp[sl], W.old_stem[0], None, W.old_stem[0].shape[0], mask_aux=o[sl], out=o[sl])
     nb = len(W.blocks)
-    tail = disc_tail_start(W, x.shape[2], x.shape[3])
     for i, (w1, b1, w2, b2) in enumerate(W.blocks):
-        inp, a1, q1, a2 = saved[i]
+        inp, a1, q1, a2 = saved[i].rows(sl)
         c1 = w1.shape[0]
         if a1.dtype == torch.uint8:
-            cache.conv(inp[sl], w1, False, None, c1, mask_aux=a1[sl], pool_out=q1[sl])
+            cache.conv(inp, w1, False, None, c1, mask_aux=a1, pool_out=q1)
         else:
-            cache.conv(inp[sl], w1, False, None, c1, mask_aux=a1[sl], out=a1[sl], pool_out=q1[sl])
-        if tail is not None and i == tail:  # the rest of the tangent pass (<= 4x4 maps) in one launch, in place as well
-            _disc_tail_forward(W, tail, q1[sl], cache, False, masks=[tuple(u[sl] for u in saved[j]) for j in range(tail, nb)])
+            cache.conv(inp, w1, False, None, c1, mask_aux=a1, out=a1, pool_out=q1)
+        if i == ctx.tail:  # the rest of the tangent pass (<= 4x4 maps) in one launch, in place as well
+            _disc_tail_forward(W, i, q1, cache, False, masks=[saved[j].rows(sl) for j in range(i, nb)])
             break
         if a2.dtype == torch.uint8:  # fade-in block with the blend fused: straight into the next block's input slice
             F = FadeIn.of(alpha)
-            ops.conv3x3_fade(q1[sl], cache.get_wino(w2, False), None, c1, _lib.MG_FADE_TANGENT, o[sl], F.coef(x.device),
-                             mask_in=a2[sl], out=saved[1][0][sl])
+            ops.conv3x3_fade(q1, cache.get_wino(w2, False), None, c1, _lib.MG_FADE_TANGENT, o[sl], F.coef(x.device),
+                             mask_in=a2, out=saved[1].inp[sl])
             continue
-        cache.conv(q1[sl], w2, False, None, c1, mask_aux=a2[sl], out=a2[sl])
+        cache.conv(q1, w2, False, None, c1, mask_aux=a2, out=a2)
         if i == 0 and W.old_stem is not None:
-            target = saved[1][0][sl] if nb > 1 else flat[sl].reshape(a2[sl].shape)
+            target = saved[1].inp[sl] if nb > 1 else ctx.flat[sl].reshape(a2.shape)
             F = FadeIn.of(alpha)
-            ops.axpby(F.a, a2[sl], F.b, o[sl], out=target, coef=F.dev)
+            ops.axpby(F.a, a2, F.b, o[sl], out=target, coef=F.dev)
     # ---- one weight-gradient sweep over the 3N samples
     for i, (w1, b1, w2, b2) in enumerate(W.blocks):
-        inp, a1, q1, a2 = saved[i]
-        gpre1, gpre2 = hs["blocks"][i]
-        gw1, acc = sink.slot(w1)
-        gb1, _ = sink.slot(b1)
-        ops.conv3x3_wgrad(inp, gpre1, gw1, gb1, accumulate=acc, bias_n=2 * n, defer=defer)
-        gw2, acc = sink.slot(w2)
-        gb2, _ = sink.slot(b2)
-        ops.conv3x3_wgrad(q1, gpre2, gw2, gb2, accumulate=acc, bias_n=2 * n, defer=defer)
+        gpre1, gpre2 = hs.blocks[i]
+        sink.conv3x3(w1, b1, saved[i].inp, gpre1, bias_n=2 * n, defer=defer)
+        sink.conv3x3(w2, b2, saved[i].q1, gpre2, bias_n=2 * n, defer=defer)
     # x = [real | fake | u_0], gy = [delta_real | delta_fake | h_0]: one launch per stem, bias gradient from the first 2N samples
-    gws, acc = sink.slot(W.stem[0])
-    gbs, _ = sink.slot(W.stem[1])
-    ops.conv1x1_wgrad(x, hs["stem"], gws, gbs, accumulate=acc, bias_n=2 * n)
+    sink.conv1x1(W.stem[0], W.stem[1], x, hs.stem, bias_n=2 * n)
     if W.old_stem is not None:
-        gwo, acc = sink.slot(W.old_stem[0])
-        gbo, _ = sink.slot(W.old_stem[1])
-        ops.conv1x1_wgrad(xp, hs["old"], gwo, gbo, accumulate=acc, bias_n=2 * n)
-    gwc, acc = sink.slot(W.clf[0])
-    gbc, _ = sink.slot(W.clf[1])
-    ops.linear1_bwd(flat, W.clf[0], g_out, gw=gwc, gb=gbc, need_gx=False, accumulate=acc, bias_n=2 * n)
+        sink.conv1x1(W.old_stem[0], W.old_stem[1], xp, hs.old, bias_n=2 * n)
+    sink.linear(W.clf[0], W.clf[1], ctx.flat, g_out, need_gx=False, bias_n=2 * n)
     if defer is not None:
         defer.flush()  # the slab reductions of every Winograd weight gradient of the sweep, one launch
     stats = ops.group_means(out, 3)  # [mean D(real), mean D(fake), mean D(x~), -(mean D(real) - mean D(fake))]

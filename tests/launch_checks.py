@@ -42,8 +42,9 @@ def _launch(name: str) -> bool:
     return not name.endswith("_supported") and name not in NOT_PER_LAUNCH
 
 
-def step_census(monkeypatch, level, batch):
-    """The routing census of one critic + one generator update at (level, batch), alpha 0.5 (eager: MG_GRAPHS=0)."""
+def step_census(monkeypatch, level, batch, fused_d_step=True):
+    """The routing census of one critic + one generator update at (level, batch), alpha 0.5 (eager: MG_GRAPHS=0);
+    `fused_d_step=False`: through the modules and autograd instead of the two fused steps."""
     import bench
     from musicgan_amd.optim import FusedAdam
     from musicgan_amd.train_step import ProGANStepper
@@ -51,7 +52,7 @@ def step_census(monkeypatch, level, batch):
     gen, disc = bench.build_nets(level, 32, DEV)
     og = FusedAdam(gen.parameters(), lr=1e-3, betas=(0.0, 0.9))
     od = FusedAdam(disc.parameters(), lr=1e-3, betas=(0.0, 0.9))
-    st = ProGANStepper(gen, disc, og, od, 32)
+    st = ProGANStepper(gen, disc, og, od, 32, fused_d_step=fused_d_step)
     side = bench.LEVEL_SIDE[level]
     rng = torch.Generator(device=DEV).manual_seed(1234)
     x_real = torch.rand(batch, 2, side, side, device=DEV, generator=rng) * 2 - 1

@@ -48,10 +48,9 @@ else:
     x_real, alpha = torch.from_numpy(g["x_real"]), float(g["alpha"])
 with torch.no_grad():
     out, ctx = engine.disc_forward(disc._weights(), x_real.cuda().contiguous(), alpha, disc._pack_cache, save=True)
-_, h0, saved, _, _, _, _ = ctx
-ours = {"h0": h0, "out": out}
-for j, s in enumerate(saved):
-    ours[f"a1_{j}"], ours[f"a2_{j}"] = s[1], s[3]
+ours = {"h0": ctx.h0, "out": out}
+for j, s in enumerate(ctx.saved):
+    ours[f"a1_{j}"], ours[f"a2_{j}"] = s.a1, s.a2
 r64, r32 = cpu_acts(ds, x_real, alpha, torch.float64), cpu_acts(ds, x_real, alpha, torch.float32)
 print(f"{'layer':8s} {'shape':22s} {'rms':>9s} {'ours-64/rms':>12s} {'fp32-64/rms':>12s} {'ratio':>6s} {'flips ours':>10s} {'flips fp32':>10s}")
 for k, ref in r64.items():
