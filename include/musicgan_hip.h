@@ -738,6 +738,20 @@ int mg_nn_sqdist(const float* q, const float* r, const double* qn, const double*
 int mg_nn_merge(const double* dist, const int64_t* qid, const int64_t* rid, double* best_d, int64_t* best_i, int64_t nq, int64_t nr,
                 int k, mg_stream_t stream);
 
+/* ---- precision / recall / density / coverage (csrc/prdc.hip): the kernels behind nn_ops.nn_sqdist_tiled / prdc_scan and
+ * metrics.PRDC, which the reference does not have (definition: DESIGN.md 4.14).
+ * tiled_ws_bytes: HOST query, the float64 slice sums of one sqdist_tiled launch: 16 x nq x nr, whatever D is.
+ * sqdist_tiled:   mg_nn_sqdist's arguments and, bit for bit, its output for any nq, nr, D >= 1 and any alignment of the rows: the same
+ *                 float32 chains inside chunks and the same float64 order across them, with the operand rows staged in LDS and shared
+ *                 by 128 x 128 pairs.  All of dist (nq,nr) is written; ws must be 8-byte aligned.
+ * scan:           for every row i of dist (nq,nr) float64: count[i] += #{ j : dist[i][j] <= radius[j] } (int64) and rowmin[i] =
+ *                 min(rowmin[i], min_j dist[i][j]), both accumulated in place, so a matrix may go through in column blocks.  One
+ *                 writer per row, no atomics: counts are integers and the minimum is exact, so the blocking does not show. */
+size_t mg_nn_tiled_ws_bytes(int64_t nq, int64_t nr, int64_t D);
+int mg_nn_sqdist_tiled(const float* q, const float* r, const double* qn, const double* rn, int64_t nq, int64_t nr, int64_t D,
+                       double* dist, void* ws, size_t ws_bytes, mg_stream_t stream);
+int mg_prdc_scan(const double* dist, const double* radius, int64_t* count, double* rowmin, int64_t nq, int64_t nr, mg_stream_t stream);
+
 /* ---- DiffAugment (csrc/diffaug.hip, csrc/diffaug_plan.h): one random translation with zero fill and one random cutout per sample,
  * applied to every image the critic sees, and the adjoint for the generator's gradient (definition: DESIGN.md 4.13; the kernels behind
  * musicgan_amd/aug_ops.py).  x, y, gy, gx are (n, c, h, w) float32; u is (n, 8) float32 in [0, 1) in DEVICE memory, read by the kernel:

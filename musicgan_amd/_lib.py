@@ -226,6 +226,9 @@ SIGNATURES = {
     "mg_nn_sqnorm": (c_int, [_P, c_int64, c_int64, _P, _P]),
     "mg_nn_sqdist": (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_int64, _P, _P, c_size_t, _P]),
     "mg_nn_merge": (c_int, [_P, _P, _P, _P, _P, c_int64, c_int64, c_int, _P]),
+    "mg_nn_tiled_ws_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "mg_nn_sqdist_tiled": (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_int64, _P, _P, c_size_t, _P]),
+    "mg_prdc_scan": (c_int, [_P, _P, _P, _P, c_int64, c_int64, _P]),
     "mg_diffaug_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P]),
     "mg_diffaug_bwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P]),
     "mg_diffaug_decode": (c_int, [_P, c_int, c_int, c_int, c_int, c_float, _P]),

@@ -24,14 +24,13 @@
 //            (DBL_MAX, -1), which every candidate beats.
 #include <cfloat>
 
-#include "mg_common.h"
+#include "nn_common.h"
 
 namespace {
 
-constexpr int NN_CHUNK = 256;                  // components one wave accumulates in float32
 constexpr int NN_TQ = 2;                       // 16-query tiles per wave
 constexpr int NN_QB = 16 * NN_TQ * 4;          // queries per workgroup of 4 waves
-constexpr int NN_SLICES = 16, NN_MAXK = 16;
+constexpr int NN_MAXK = 16;
 
 __device__ __forceinline__ double nn_block_sum(double v, double* red) {  // fixed tree over the 256 threads; the sum in thread 0
   red[threadIdx.x] = v;
@@ -53,19 +52,6 @@ __global__ void __launch_bounds__(256) nn_sqnorm_k(const float* __restrict__ x, 
   }
   s = nn_block_sum(s, red);
   if (threadIdx.x == 0) out[blockIdx.x] = s;
-}
-
-// 4 consecutive components of a row from k on; zero from D on.  VEC: D % 4 == 0 and 16-byte aligned rows, so k < D covers all four.
-template <bool VEC>
-__device__ __forceinline__ f32x4 nn_load4(const float* __restrict__ row, long long k, long long D) {
-  if constexpr (VEC) {
-    return k < D ? *reinterpret_cast<const f32x4*>(row + k) : f32x4{0.f, 0.f, 0.f, 0.f};
-  } else {
-    f32x4 v;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) v[u] = k + u < D ? row[k + u] : 0.f;
-    return v;
-  }
 }
 
 template <bool VEC>
@@ -165,8 +151,6 @@ __global__ void __launch_bounds__(64) nn_merge_k(const double* __restrict__ dist
     best_i[qi * k + s] = si[s][t];
   }
 }
-
-long long nn_chunks(long long D) { return (D + NN_CHUNK - 1) / NN_CHUNK; }
 
 }  // namespace
 

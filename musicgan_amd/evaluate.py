@@ -5,31 +5,36 @@ in the paper, lower is better.  With "msssim" among `metrics` it also reports MS
 next to the same number for pairs of real images: a generated value well above the real one means the generator repeats itself
 (mode collapse), which SWD does not show.  With "nn" it reports how far generated images are from their nearest dataset image,
 next to the same number for real images against the rest of the dataset: a generator that replays its corpus scores perfectly on
-the other two and near zero here.  Single GPU."""
+the other two and near zero here.  With "prdc" it reports k-nearest-neighbour precision / recall / density / coverage of all
+generated against all real images: which way a checkpoint is wrong -- off the data manifold, or on it but covering part of it.
+Single GPU."""
 import json
 from typing import Dict, Optional, Sequence
 
 import torch
 
 from . import audio, ops
-from .metrics import MSSSIM, SWD, NearestNeighbours
+from .metrics import MSSSIM, PRDC, SWD, NearestNeighbours
 from .networks import Generator
 
 _FINAL_LEVEL, _FULL_SIDE = 7, 512
 _LATENT_H, _LATENT_W = 2, 2
 METRICS = ("swd", "msssim", "nn")
+METRICS_ALL = METRICS + ("prdc",)
 # the nearest-neighbour check: queries per set, the side images are compared at (pixel L2 at 512 x 512 is dominated by sub-pixel
 # shifts and would cost 16 x more than the rest of the evaluation), neighbours kept per query
 _NN_QUERIES, _NN_SIDE, _NN_K = 256, 128, 1
+_PRDC_K = 3   # neighbours that define a sample's ball (Kynkaanniemi et al. 2019; also the 3 of StyleGAN2's tables); the side is _NN_SIDE
 
 
 def evaluate(gen_dict_state: str, rand_channels: int, input_dataset: str, metrics: Sequence[str] = ("swd",), *,
              level: int = _FINAL_LEVEL, nb_images: int = 8192, batch_size: int = 16, seed: int = 0,
              output: Optional[str] = None) -> Dict[str, float]:
     """`level`: the growth level the checkpoint was saved at (7 = fully grown, 512 x 512); real samples are brought to that level's
-    side by the training loop's own input transform.  `metrics`: a subset of ("swd", "msssim", "nn").  Returns {"<side>": swd, ...,
-    "avg": swd, "msssim_real": .., "msssim_fake": .., "nn_fake": .., "nn_real": .., "nn_fake_min": .., "nn_real_min": ..} (the keys
-    of the metrics asked for) and writes it as JSON to `output`.
+    side by the training loop's own input transform.  `metrics`: a subset of ("swd", "msssim", "nn", "prdc").  Returns {"<side>": swd, ...,
+    "avg": swd, "msssim_real": .., "msssim_fake": .., "nn_fake": .., "nn_real": .., "nn_fake_min": .., "nn_real_min": .., "precision": ..,
+    "recall": .., "density": .., "coverage": .., "precision_real": .., .., "coverage_real": ..} (the keys of the metrics asked for)
+    and writes it as JSON to `output`.
 
     "nn": the first min(nb_images, 256) generated images and as many real ones (random dataset entries, each barred from matching
     itself) are compared with all `nb_images` real images at min(side, 128) pixels a side (larger images are reduced by 2 x 2
@@ -37,14 +42,22 @@ def evaluate(gen_dict_state: str, rand_channels: int, input_dataset: str, metric
     mean over the queries, `nn_fake_min` / `nn_real_min` the smallest (one memorised sample does not move a mean).  `nn_fake`
     well below `nn_real`, or `nn_fake_min` near 0, means memorisation.  Consecutive dataset entries are adjacent chunks of one
     track, so a real image's nearest neighbour is often its own continuation and `nn_real` is small: that is the honest
-    calibration -- it is the distance at which the data resembles itself."""
+    calibration -- it is the distance at which the data resembles itself.
+
+    "prdc": all `nb_images` generated images against all `nb_images` real ones, reduced as for "nn", with balls reaching to the
+    3rd nearest other member of the own set (metrics.PRDC).  Appends `precision` (share of generated images inside some real
+    image's ball: low = samples off the data manifold), `recall` (share of real images inside some generated image's ball: low =
+    modes missing), `density` and `coverage` (their outlier-robust successors), then `precision_real` .. `coverage_real`: the same
+    four between two disjoint random halves of the real set, which is what a perfect generator would score on this corpus."""
     if not 0 <= level <= _FINAL_LEVEL:
         raise ValueError(f"level must be in 0 .. {_FINAL_LEVEL}, got {level}")
     if nb_images < 1 or batch_size < 1:
         raise ValueError("nb_images and batch_size must be positive")
     metrics = tuple(metrics)
-    if not metrics or any(m not in METRICS for m in metrics) or len(set(metrics)) != len(metrics):
-        raise ValueError(f"metrics: a non-empty subset of {METRICS} expected, got {metrics}")
+    if not metrics or any(m not in METRICS_ALL for m in metrics) or len(set(metrics)) != len(metrics):
+        raise ValueError(f"metrics: a non-empty subset of {METRICS_ALL} expected, got {metrics}")
+    if "prdc" in metrics and nb_images < 2 * (_PRDC_K + 1):
+        raise ValueError(f"prdc needs at least {2 * (_PRDC_K + 1)} images (two halves of k + 1 = {_PRDC_K + 1}), got {nb_images}")
     side = _FULL_SIDE >> (_FINAL_LEVEL - level)
     device = torch.device("cuda", torch.cuda.current_device())
 
@@ -61,6 +74,8 @@ def evaluate(gen_dict_state: str, rand_channels: int, input_dataset: str, metric
         raise ValueError(f"MS-SSIM needs at least 2 images to pair, got {nb_images}")
     if "nn" in metrics and nb_images < 2:
         raise ValueError(f"nearest neighbours need at least 2 images (a real query may not match itself), got {nb_images}")
+    if "prdc" in metrics and nb_images < 2 * (_PRDC_K + 1):
+        raise ValueError(f"prdc needs at least {2 * (_PRDC_K + 1)} images (two halves of k + 1 = {_PRDC_K + 1}), got {nb_images}")
 
     print(f"Evaluate {nb_images} real and {nb_images} generated images of {side} x {side}...")
     rng = torch.Generator(device=device).manual_seed(seed)
@@ -78,7 +93,7 @@ def evaluate(gen_dict_state: str, rand_channels: int, input_dataset: str, metric
         result.update(swd.result())
         for name, value in result.items():
             print(f"SWD x 1e3 [{name:>3}] = {value:.4f}")
-    if "msssim" in metrics or "nn" in metrics:   # one seeded order of the dataset, shared by both
+    if "msssim" in metrics or "nn" in metrics or "prdc" in metrics:   # one seeded order of the dataset, shared by all three
         perm = torch.randperm(nb_images, generator=torch.Generator().manual_seed(seed)).tolist()
     if "msssim" in metrics:
         # random pairs, the same index pairs for both sets: consecutive dataset samples are adjacent chunks of one track, and
@@ -101,8 +116,8 @@ def evaluate(gen_dict_state: str, rand_channels: int, input_dataset: str, metric
         result["msssim_real"], result["msssim_fake"] = ms_real.result(), ms_fake.result()
         for name in ("msssim_real", "msssim_fake"):
             print(f"MS-SSIM [{name[7:]}] = {result[name]:.6f}")
-    if "nn" in metrics:
-        nq, cside = min(nb_images, _NN_QUERIES), min(side, _NN_SIDE)
+    if "nn" in metrics or "prdc" in metrics:   # both compare images reduced to at most _NN_SIDE pixels a side
+        cside = min(side, _NN_SIDE)
 
         def reduced(x):
             while x.shape[-1] > cside:
@@ -112,6 +127,8 @@ def evaluate(gen_dict_state: str, rand_channels: int, input_dataset: str, metric
         def real_at(idx):
             return reduced(ops.input_transform(torch.stack([dataset[i] for i in idx]).to(device).contiguous(), side))
 
+    if "nn" in metrics:
+        nq = min(nb_images, _NN_QUERIES)
         with torch.no_grad():
             fake_q = torch.cat([reduced(gen(latents[lo:lo + batch_size].contiguous(), 1.0).contiguous())
                                 for lo in range(0, nq, batch_size)])[:nq].contiguous()
@@ -131,6 +148,28 @@ def evaluate(gen_dict_state: str, rand_channels: int, input_dataset: str, metric
         for name in ("fake", "real"):
             print(f"NN RMS [{name}] = {result['nn_' + name]:.6f} (smallest {result['nn_' + name + '_min']:.6f}) at {cside} x {cside}")
         print("NN: fake well below real, or a smallest fake value near 0, means memorised training samples")
+    if "prdc" in metrics:
+        need, free = 2 * nb_images * 2 * cside * cside * 4, torch.cuda.mem_get_info(device)[0]
+        if need > 0.75 * free:
+            raise ValueError(f"prdc keeps {nb_images} real and {nb_images} generated images of {cside} x {cside} resident: {need} "
+                             f"bytes, more than three quarters of the {free} bytes free on the device")
+        half = nb_images // 2
+        with torch.no_grad():
+            prdc = PRDC(k=_PRDC_K)
+            for lo in range(0, nb_images, batch_size):
+                prdc.feed_real(real_at(list(range(lo, min(lo + batch_size, nb_images)))))
+                prdc.feed_fake(reduced(gen(latents[lo:lo + batch_size].contiguous(), 1.0).contiguous()))
+            result.update(prdc.result())
+            prdc = PRDC(k=_PRDC_K)   # the data against itself: two disjoint random halves (the first pair of sets is released)
+            for lo in range(0, half, batch_size):
+                prdc.feed_real(real_at(perm[lo:min(lo + batch_size, half)]))
+                prdc.feed_fake(real_at(perm[half + lo:min(half + lo + batch_size, 2 * half)]))
+            result.update({name + "_real": value for name, value in prdc.result().items()})
+        for suffix in ("", "_real"):
+            for name in PRDC.KEYS:
+                print(f"PRDC [{name + suffix:>14}] = {result[name + suffix]:.6f} at {cside} x {cside}, k = {_PRDC_K}")
+        print("PRDC: low precision means samples off the data manifold, low recall or coverage means modes missing; compare with "
+              "the _real column (two halves of the data against each other)")
     if output is not None:
         with open(output, "w") as f:
             json.dump(result, f, indent=1)

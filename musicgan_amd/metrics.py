@@ -27,7 +27,17 @@ distances between flattened float32 images, exact to a derived bound at any size
     nn = NearestNeighbours(queries, k=1)          # float32 cuda (Q, ...), kept resident; query_ids: leave-one-out
     for batch, ids in dataset:  nn.feed(batch, ids)   # (B, ...) of the same trailing shape, B distinct ids >= 0, any split / order
     dist, idx = nn.result()                       # (Q, k) float64 squared distances ascending, (Q, k) int64 ids; both cuda
-    pairwise_sqdist(a, b)                         # the (Na, Nb) float64 distance matrix on its own"""
+    pairwise_sqdist(a, b)                         # the (Na, Nb) float64 distance matrix on its own
+
+(4) Precision / recall (Kynkaanniemi et al., NeurIPS 2019) and density / coverage (Naeem et al., ICML 2020) in pixel space: which
+way is a generator wrong -- samples off the data manifold, or on it but covering only part of it?  Definition: DESIGN.md 4.14;
+kernels: csrc/prdc.hip (and the merge of csrc/nn.hip) through musicgan_amd/nn_ops.py.
+
+    prdc = PRDC(k=3)
+    for batch in real:  prdc.feed_real(batch)     # float32 cuda (B, ...), one trailing shape, any split, any interleaving
+    for batch in fake:  prdc.feed_fake(batch)
+    prdc.result()                                 # {"precision": .., "recall": .., "density": .., "coverage": ..}
+    prdc.per_sample()                             # the radii, ball counts and nearest-fake distances behind them, on the device"""
 from __future__ import annotations
 
 import operator
@@ -407,3 +417,101 @@ class NearestNeighbours:
         if bool((self._best_i[:, -1] < 0).any()):   # a query whose own id was among fewer than k + 1 references
             raise ValueError(f"{self._fed} references fed: some query has fewer than {self.k} neighbours that are not itself")
         return self._best_d.clone(), self._best_i.clone()
+
+
+# ------------------------------------------------------------------ precision / recall / density / coverage
+class PRDC:
+    """k-nearest-neighbour manifold metrics between a real and a fake set of images, on squared L2 distances in pixel space.
+    radius(x) = the distance from x to its k-th nearest OTHER member of its own set (leave-one-out by position);
+    precision = the share of fakes inside some real ball, recall = the share of reals inside some fake ball,
+    density = the number of real balls a fake lies in, averaged and divided by k, coverage = the share of reals whose nearest
+    fake is inside their own ball.  Feeding keeps a device copy and launches nothing else; the matrices real x real, fake x fake,
+    fake x real and real x fake go through nn_sqdist_tiled in row blocks of at most `block_bytes` (distance block plus kernel
+    workspace) when the result is first asked for.  A pair's distance depends on its two rows alone, the radii come from a merge
+    ordered by (distance, position), counts are integers and minima exact: every output is the same bit for bit for any split
+    and order of the feeds and any `block_bytes`."""
+
+    KEYS = ("precision", "recall", "density", "coverage")
+
+    def __init__(self, k: int = 3, block_bytes: int = 256 << 20) -> None:
+        if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= nn_ops.MAX_K:
+            raise ValueError(f"k in 1 .. {nn_ops.MAX_K} expected, got {k}")
+        if block_bytes < 1:
+            raise ValueError(f"block_bytes must be positive, got {block_bytes}")
+        self.k, self.block_bytes, self.shape = k, int(block_bytes), None
+        self._fed = {"real": [], "fake": []}
+        self._n = {"real": 0, "fake": 0}
+        self._per_sample = None
+
+    def _feed(self, which: str, batch: torch.Tensor) -> None:
+        if batch.dim() < 2 or batch.shape[0] < 1 or batch[0].numel() < 1:
+            raise ValueError(f"feed_{which}: a non-empty batch (B, ...) expected, got {tuple(batch.shape)}")
+        if self.shape is not None and tuple(batch.shape[1:]) != self.shape:
+            raise ValueError(f"feed_{which}: a batch (B, {', '.join(map(str, self.shape))}) expected, got {tuple(batch.shape)}")
+        rows = _rows(batch, f"PRDC.feed_{which}")
+        self.shape = tuple(batch.shape[1:])
+        self._fed[which].append(rows.clone())
+        self._n[which] += rows.shape[0]
+        self._per_sample = None
+
+    def feed_real(self, batch: torch.Tensor) -> None:
+        self._feed("real", batch)
+
+    def feed_fake(self, batch: torch.Tensor) -> None:
+        self._feed("fake", batch)
+
+    def _block_rows(self, nr: int, d: int) -> int:
+        per_row = 8 * nr + nn_ops.nn_tiled_ws_bytes(1, nr, d)
+        return max(1, self.block_bytes // per_row)
+
+    def _radius(self, x: torch.Tensor, xn: torch.Tensor) -> torch.Tensor:
+        """every row's distance to its k-th nearest other row of x"""
+        n, d, dev = x.shape[0], x.shape[1], x.device
+        ids = torch.arange(n, dtype=torch.int64, device=dev)
+        best_d = torch.full((n, self.k), nn_ops.EMPTY, dtype=torch.float64, device=dev)
+        best_i = torch.full((n, self.k), -1, dtype=torch.int64, device=dev)
+        step = self._block_rows(n, d)
+        for lo in range(0, n, step):
+            hi = min(lo + step, n)
+            dist = nn_ops.nn_sqdist_tiled(x[lo:hi], x, xn[lo:hi], xn)
+            nn_ops.nn_merge(dist, ids, best_d[lo:hi], best_i[lo:hi], ids[lo:hi])
+        return best_d[:, self.k - 1].contiguous()
+
+    def _scan(self, q: torch.Tensor, qn: torch.Tensor, r: torch.Tensor, rn: torch.Tensor, radius: torch.Tensor):
+        """(count, rowmin) of every row of q against the balls of r"""
+        nq, nr, d, dev = q.shape[0], r.shape[0], q.shape[1], q.device
+        count = torch.zeros(nq, dtype=torch.int64, device=dev)
+        rowmin = torch.full((nq,), float("inf"), dtype=torch.float64, device=dev)
+        step = self._block_rows(nr, d)
+        for lo in range(0, nq, step):
+            hi = min(lo + step, nq)
+            dist = nn_ops.nn_sqdist_tiled(q[lo:hi], r, qn[lo:hi], rn)
+            nn_ops.prdc_scan(dist, radius, count[lo:hi], rowmin[lo:hi])
+        return count, rowmin
+
+    def per_sample(self) -> Dict[str, torch.Tensor]:
+        """device tensors: radius_real / radius_fake (float64, the k-th nearest other member of the own set), count_fake (int64,
+        per fake: the real balls it lies in), count_real (int64, per real: the fake balls it lies in), nearest_fake (float64, per
+        real: the distance to the nearest fake)"""
+        if min(self._n.values()) < self.k + 1:
+            raise ValueError(f"{self._n['real']} real and {self._n['fake']} fake images fed, at least k + 1 = {self.k + 1} of each "
+                             "expected")
+        if self._per_sample is None:
+            real, fake = (torch.cat(self._fed[w]) if len(self._fed[w]) > 1 else self._fed[w][0] for w in ("real", "fake"))
+            self._fed = {"real": [real], "fake": [fake]}
+            rn, fn = nn_ops.nn_sqnorm(real), nn_ops.nn_sqnorm(fake)
+            radius_real, radius_fake = self._radius(real, rn), self._radius(fake, fn)
+            count_fake, _ = self._scan(fake, fn, real, rn, radius_real)
+            count_real, nearest_fake = self._scan(real, rn, fake, fn, radius_fake)
+            self._per_sample = dict(radius_real=radius_real, radius_fake=radius_fake, count_fake=count_fake, count_real=count_real,
+                                    nearest_fake=nearest_fake)
+        return dict(self._per_sample)
+
+    def result(self) -> Dict[str, float]:
+        p = self.per_sample()
+        n_real, n_fake = self._n["real"], self._n["fake"]
+        # four integer sums on the device, one copy, the divisions on the host: exact counts over exact divisors
+        inside, seen, balls, covered = torch.stack([(p["count_fake"] > 0).sum(), (p["count_real"] > 0).sum(), p["count_fake"].sum(),
+                                                    (p["nearest_fake"] <= p["radius_real"]).sum()]).tolist()
+        return {"precision": inside / n_fake, "recall": seen / n_real, "density": balls / (self.k * n_fake),
+                "coverage": covered / n_real}
