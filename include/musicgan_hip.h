@@ -770,6 +770,28 @@ int mg_diffaug_fwd(const float* x, const float* u, int n, int c, int h, int w, i
 int mg_diffaug_bwd(const float* gy, const float* u, int n, int c, int h, int w, int ops, float p, float* gx, mg_stream_t stream);
 int mg_diffaug_decode(const float* u_host, int n, int h, int w, int ops, float p, int32_t* out);
 
+/* ---- k-means bins for NDB / JSD (csrc/kmeans.hip): the kernels behind musicgan_amd/km_ops.py and metrics.KMeans / metrics.NDB, which
+ * the reference does not have (definition: DESIGN.md 4.15).  The distances of a Lloyd iteration are mg_nn_sqdist_tiled's; these are the
+ * rest.  1 <= k <= 1024 everywhere; labels are int32 bin numbers; nothing is read back to the host and nothing is allocated.
+ * assign:          for every row i of dist (n,k) float64: label[i] = the column of the row's smallest entry (ties: the smaller column),
+ *                  mind[i] = that entry; changed[0] (int64) = the number of rows whose label was rewritten with a different value,
+ *                  overwritten, not accumulated.
+ * order:           the positions 0 .. n-1 sorted by (label, position) into order (n,) int32, and the exclusive prefix sums of the bin
+ *                  sizes into start (k+1,) int32; every element of both is written (positions whose label is outside 0 .. k-1 come
+ *                  last, behind start[k]).  n <= 2^20, MG_EINVAL beyond.
+ * update_ws_bytes: HOST query, the float64 partial sums of one update: (n / 32 + k) x d.
+ * update:          centroid[j] (k,d) float32 = the float64 sum of x's rows order[start[j] .. start[j+1]) in that order, in chunks of 32
+ *                  members added in chunk order, divided in float64 by the member count and rounded once to float32; a bin without
+ *                  members keeps its centroid.  A centroid depends on its ordered member list alone.  16-byte loads when d % 4 == 0 and
+ *                  x is 16-byte aligned, element-wise loads otherwise.  n <= 2^20.
+ * count:           count[label[i]] += 1 for every i (count (k,) int64, accumulated in place; labels outside 0 .. k-1 are skipped). */
+int mg_km_assign(const double* dist, int64_t n, int k, int32_t* label, double* mind, int64_t* changed, mg_stream_t stream);
+int mg_km_order(const int32_t* label, int64_t n, int k, int32_t* start, int32_t* order, mg_stream_t stream);
+size_t mg_km_update_ws_bytes(int64_t n, int64_t d, int k);
+int mg_km_update(const float* x, int64_t n, int64_t d, const int32_t* order, const int32_t* start, int k, float* centroid, void* ws,
+                 size_t ws_bytes, mg_stream_t stream);
+int mg_km_count(const int32_t* label, int64_t n, int k, int64_t* count, mg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

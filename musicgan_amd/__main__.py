@@ -8,13 +8,14 @@ from fractions import Fraction
 
 _METRICS = ("swd", "msssim", "nn")
 _METRICS_ALL = _METRICS + ("prdc",)
+_METRICS_EVERY = _METRICS_ALL + ("ndb",)
 _AUGMENTS = ("translation", "cutout")   # aug_ops.OPS (not imported here: the modes are dispatched lazily)
 
 
 def _metric_list(text: str):
     names = tuple(t.strip() for t in text.split(","))
-    if any(n not in _METRICS_ALL for n in names) or len(set(names)) != len(names):
-        raise argparse.ArgumentTypeError(f"a comma-separated subset of {','.join(_METRICS_ALL)} expected, got {text!r}")
+    if any(n not in _METRICS_EVERY for n in names) or len(set(names)) != len(names):
+        raise argparse.ArgumentTypeError(f"a comma-separated subset of {','.join(_METRICS_EVERY)} expected, got {text!r}")
     return names
 
 
@@ -114,14 +115,17 @@ _MODES = {
         (("--batch-size",), dict(dest="batch_size", type=int, default=16)),
         (("--seed",), dict(type=int, default=0)),
         (("-o", "--output"), dict(type=str, default=None, help="also write the result as JSON to this file")),
-        (("--metrics",), dict(type=_metric_list, default=None, metavar="swd,msssim,nn,prdc",
+        (("--metrics",), dict(type=_metric_list, default=None, metavar="swd,msssim,nn,prdc,ndb",
                               help="what to report (default: swd); msssim: MS-SSIM between random pairs of generated images "
                                    "and of real ones -- a generated value well above the real one means mode collapse; nn: RMS "
                                    "distance to the nearest dataset image, of generated images and of real ones -- a generated "
                                    "value well below the real one, or a smallest value near 0, means memorised samples; prdc: "
                                    "k-nearest-neighbour precision / recall / density / coverage of all generated against all real "
                                    "images -- low precision means samples off the data manifold, low recall or coverage means "
-                                   "missing modes; compare with the _real figures")),
+                                   "missing modes; compare with the _real figures; ndb: the share of k-means bins of the real "
+                                   "images whose share of the generated images is statistically different, and the Jensen-Shannon "
+                                   "divergence of the two bin histograms -- ndb well above ndb_real means modes missing or "
+                                   "over-produced")),
     ], lambda a: (a.gen_dict_state, a.rand_channels, a.input_dataset),
         lambda a: dict(level=a.level, nb_images=a.nb_images, batch_size=a.batch_size, seed=a.seed, output=a.output,
                        **({"metrics": a.metrics} if a.metrics is not None else {}))),

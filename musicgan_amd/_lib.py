@@ -232,6 +232,11 @@ SIGNATURES = {
     "mg_diffaug_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P]),
     "mg_diffaug_bwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P]),
     "mg_diffaug_decode": (c_int, [_P, c_int, c_int, c_int, c_int, c_float, _P]),
+    "mg_km_assign": (c_int, [_P, c_int64, c_int, _P, _P, _P, _P]),
+    "mg_km_order": (c_int, [_P, c_int64, c_int, _P, _P, _P]),
+    "mg_km_update_ws_bytes": (c_size_t, [c_int64, c_int64, c_int]),
+    "mg_km_update": (c_int, [_P, c_int64, c_int64, _P, _P, c_int, _P, _P, c_size_t, _P]),
+    "mg_km_count": (c_int, [_P, c_int64, c_int, _P, _P]),
 }
 
 _lib = None

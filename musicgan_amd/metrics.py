@@ -37,15 +37,28 @@ kernels: csrc/prdc.hip (and the merge of csrc/nn.hip) through musicgan_amd/nn_op
     for batch in real:  prdc.feed_real(batch)     # float32 cuda (B, ...), one trailing shape, any split, any interleaving
     for batch in fake:  prdc.feed_fake(batch)
     prdc.result()                                 # {"precision": .., "recall": .., "density": .., "coverage": ..}
-    prdc.per_sample()                             # the radii, ball counts and nearest-fake distances behind them, on the device"""
+    prdc.per_sample()                             # the radii, ball counts and nearest-fake distances behind them, on the device
+
+(5) NDB / JSD over k-means bins (Richardson & Weiss, "On GANs and GMMs", NeurIPS 2018; the numbers GANSynth reports): how is the
+probability mass of the samples spread over the corpus?  Bins are the Voronoi cells of a deterministic k-means on the reference
+images; every bin's share of the queries is tested against its share of the reference.  Definition: DESIGN.md 4.15; kernels:
+csrc/kmeans.hip through musicgan_amd/km_ops.py, distances through nn_ops.nn_sqdist_tiled.
+
+    km = KMeans(bins=50)
+    for batch in real:  km.feed(batch)            # float32 cuda (B, ...), one trailing shape, any split; the ORDER matters
+    km.fit()                                      # launches only
+    ndb = NDB(km)
+    for batch in fake:  ndb.feed(batch)           # assigned and counted, not kept
+    ndb.result()                                  # {"ndb": share of statistically different bins, "jsd": of the two histograms}"""
 from __future__ import annotations
 
+import math
 import operator
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
-from . import nn_ops, ops, ssim_ops
+from . import km_ops, nn_ops, ops, ssim_ops
 
 
 def pyramid_sides(side_h: int, side_w: int, min_side: int = 16) -> List[Tuple[int, int]]:
@@ -515,3 +528,200 @@ class PRDC:
                                                     (p["nearest_fake"] <= p["radius_real"]).sum()]).tolist()
         return {"precision": inside / n_fake, "recall": seen / n_real, "density": balls / (self.k * n_fake),
                 "coverage": covered / n_real}
+
+
+# ------------------------------------------------------------------ NDB / JSD over k-means bins
+NDB_Z = 1.959963984540054   # |z| beyond which a bin is different: two-sided at 0.05, the paper's level
+
+
+def _is_int(v) -> bool:
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+def ndb_statistics(reference: Sequence[int], query: Sequence[int]) -> Dict[str, object]:
+    """The statistics of DESIGN.md 4.15 from the bin counts of the reference set and of the query set, in host float64: per bin the
+    two-proportion z value (0 where the pooled standard error is 0), `different` = the bins with |z| > NDB_Z, `ndb` = different / K,
+    `jsd` = the Jensen-Shannon divergence of the two histograms (natural logarithm).  {"ndb", "jsd", "different", "z"}."""
+    try:
+        a, b = [operator.index(v) for v in reference], [operator.index(v) for v in query]
+    except TypeError:
+        raise ValueError("bin counts: integers expected") from None
+    if len(a) != len(b) or len(a) < 1 or min(a + b) < 0:
+        raise ValueError(f"two vectors of non-negative counts over the same bins expected, got {len(a)} and {len(b)} entries")
+    n_a, n_b = sum(a), sum(b)
+    if n_a < 1 or n_b < 1:
+        raise ValueError(f"{n_a} reference and {n_b} query samples counted, at least one of each expected")
+    z, jsd = [], 0.0
+    for a_j, b_j in zip(a, b):
+        big_p, big_q, p = a_j / n_a, b_j / n_b, (a_j + b_j) / (n_a + n_b)
+        se = math.sqrt(p * (1.0 - p) * (1.0 / n_a + 1.0 / n_b))
+        z.append((big_p - big_q) / se if se > 0.0 else 0.0)
+        m = 0.5 * (big_p + big_q)
+        if big_p > 0.0:
+            jsd += 0.5 * big_p * math.log(big_p / m)
+        if big_q > 0.0:
+            jsd += 0.5 * big_q * math.log(big_q / m)
+    different = sum(1 for v in z if abs(v) > NDB_Z)
+    return {"ndb": different / len(a), "jsd": max(jsd, 0.0), "different": different, "z": z}
+
+
+class KMeans:
+    """Deterministic k-means (Lloyd) on squared L2 distances in pixel space: `bins` centroids, `iterations` rounds of assignment and
+    update, then one final assignment; no early stop.  The initial centroids are the fed rows `init_ids` (distinct positions), or
+    the first `bins` entries of torch.randperm(n) from a CPU generator seeded with `seed`.  Feeding keeps a device copy; fit()
+    launches kernels only.  Distances go through nn_sqdist_tiled in row blocks of at most `block_bytes` (distance block plus kernel
+    workspace); a pair's value depends on its two rows alone, ties go to the smaller bin, a centroid is a float64 sum over its
+    members in ascending position: every output is the same bit for bit for any split of the feeds and any `block_bytes`.  The
+    ORDER of the feeds is part of the input: it sets the positions, with them the initial centroids and the order of every sum."""
+
+    def __init__(self, bins: int, iterations: int = 25, seed: int = 0, init_ids=None, block_bytes: int = 256 << 20) -> None:
+        if not _is_int(bins) or not 2 <= bins <= km_ops.MAX_K:
+            raise ValueError(f"bins in 2 .. {km_ops.MAX_K} expected, got {bins}")
+        if not _is_int(iterations) or iterations < 1:
+            raise ValueError(f"iterations >= 1 expected, got {iterations}")
+        if not _is_int(seed):
+            raise ValueError(f"an integer seed expected, got {seed}")
+        if not _is_int(block_bytes) or block_bytes < 1:
+            raise ValueError(f"block_bytes must be positive, got {block_bytes}")
+        if init_ids is not None:
+            init_ids = _id_list(init_ids, bins, "init_ids")
+            if len(set(init_ids)) != bins or min(init_ids) < 0:
+                raise ValueError(f"init_ids: {bins} distinct positions >= 0 expected")
+        self.bins, self.iterations, self.seed, self.init_ids, self.block_bytes = bins, iterations, seed, init_ids, block_bytes
+        self.shape = None
+        self._fed, self._n, self._out = [], 0, None
+
+    def feed(self, batch: torch.Tensor) -> None:
+        if batch.dim() < 2 or batch.shape[0] < 1 or batch[0].numel() < 1:
+            raise ValueError(f"feed: a non-empty batch (B, ...) expected, got {tuple(batch.shape)}")
+        if self.shape is not None and tuple(batch.shape[1:]) != self.shape:
+            raise ValueError(f"feed: a batch (B, {', '.join(map(str, self.shape))}) expected, got {tuple(batch.shape)}")
+        rows = _rows(batch, "KMeans.feed")
+        self.shape = tuple(batch.shape[1:])
+        self._fed.append(rows.clone())
+        self._n += rows.shape[0]
+        self._out = None
+
+    def _block_rows(self, d: int) -> int:
+        per_row = 8 * self.bins + nn_ops.nn_tiled_ws_bytes(1, self.bins, d)
+        return max(1, self.block_bytes // per_row)
+
+    def _assign(self, x: torch.Tensor, xn: torch.Tensor, c: torch.Tensor, labels: torch.Tensor, mind: torch.Tensor,
+                changed: torch.Tensor) -> None:
+        """labels, mind and the one-element changed of every row of x against the centroids c"""
+        n, cn, step = x.shape[0], nn_ops.nn_sqnorm(c), self._block_rows(x.shape[1])
+        if step >= n:
+            km_ops.km_assign(nn_ops.nn_sqdist_tiled(x, c, xn, cn), labels, mind, changed)
+            return
+        part = torch.empty((n + step - 1) // step, dtype=torch.int64, device=x.device)
+        for b, lo in enumerate(range(0, n, step)):
+            hi = min(lo + step, n)
+            km_ops.km_assign(nn_ops.nn_sqdist_tiled(x[lo:hi], c, xn[lo:hi], cn), labels[lo:hi], mind[lo:hi], part[b:b + 1])
+        changed.copy_(part.sum().reshape(1))
+
+    def fit(self) -> "KMeans":
+        """everything from the initial centroids to the final assignment, as launches on the current stream; the host does not wait"""
+        if self._out is not None:
+            return self
+        n, k = self._n, self.bins
+        if n < k:
+            raise ValueError(f"{n} images fed, at least as many as the {k} bins expected")
+        if n > km_ops.MAX_N:
+            raise ValueError(f"{n} images fed, at most {km_ops.MAX_N} expected")
+        ids = self.init_ids if self.init_ids is not None else \
+            torch.randperm(n, generator=torch.Generator().manual_seed(self.seed))[:k].tolist()
+        if max(ids) >= n:
+            raise ValueError(f"init_ids: positions below the {n} images fed expected, got {max(ids)}")
+        x = torch.cat(self._fed) if len(self._fed) > 1 else self._fed[0]
+        self._fed = [x]
+        dev = x.device
+        xn = nn_ops.nn_sqnorm(x)
+        c = x.index_select(0, _ids_to(ids, dev)).contiguous()
+        labels = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        mind = torch.empty(n, dtype=torch.float64, device=dev)
+        changed = torch.zeros(self.iterations + 1, dtype=torch.int64, device=dev)
+        start = torch.empty(k + 1, dtype=torch.int32, device=dev)
+        order = torch.empty(n, dtype=torch.int32, device=dev)
+        for t in range(self.iterations + 1):
+            self._assign(x, xn, c, labels, mind, changed[t:t + 1])
+            if t < self.iterations:
+                km_ops.km_order(labels, k, start, order)
+                km_ops.km_update(x, order, start, c)
+        counts = km_ops.km_count(labels, torch.zeros(k, dtype=torch.int64, device=dev))
+        self._out = dict(centroids=c, labels=labels, dist=mind, counts=counts, changed=changed)
+        return self
+
+    def _fitted(self, name: str) -> torch.Tensor:
+        if self._out is None:
+            if not self._n:
+                raise ValueError("no image fed yet")
+            self.fit()
+        return self._out[name]
+
+    @property
+    def centroids(self) -> torch.Tensor:
+        """(bins, D) float32 on the device"""
+        return self._fitted("centroids")
+
+    @property
+    def labels(self) -> torch.Tensor:
+        """(n,) int32: the bin of every fed image, by position"""
+        return self._fitted("labels")
+
+    @property
+    def counts(self) -> torch.Tensor:
+        """(bins,) int64: the bin sizes of the fed images"""
+        return self._fitted("counts")
+
+    @property
+    def changed(self) -> torch.Tensor:
+        """(iterations + 1,) int64 on the device: the labels each assignment changed (the first one: all n); 0 from convergence on"""
+        return self._fitted("changed")
+
+    def assign(self, batch: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(labels (B,) int32, dist (B,) float64) of other images against the fitted centroids: the nearest bin (ties: the smaller
+        bin) and the squared distance to its centroid"""
+        if self.shape is None:
+            raise ValueError("no image fed yet")
+        if batch.dim() < 2 or tuple(batch.shape[1:]) != self.shape or batch.shape[0] < 1:
+            raise ValueError(f"a non-empty batch (B, {', '.join(map(str, self.shape))}) expected, got {tuple(batch.shape)}")
+        rows = _rows(batch, "KMeans.assign")
+        c, dev = self.centroids, rows.device
+        labels = torch.full((rows.shape[0],), -1, dtype=torch.int32, device=dev)
+        mind = torch.empty(rows.shape[0], dtype=torch.float64, device=dev)
+        self._assign(rows, nn_ops.nn_sqnorm(rows), c, labels, mind, torch.empty(1, dtype=torch.int64, device=dev))
+        return labels, mind
+
+
+class NDB:
+    """Number of statistically Different Bins and the Jensen-Shannon divergence between the bin histogram of the images `kmeans` was
+    fitted on (the reference) and that of everything fed here.  feed() assigns a batch to its bins and adds to K counters on the
+    device; the batch is not kept and the host does not wait.  Counts are integers, so the result is the same for any split."""
+
+    KEYS = ("ndb", "jsd")
+
+    def __init__(self, kmeans: KMeans) -> None:
+        if not isinstance(kmeans, KMeans):
+            raise ValueError(f"a KMeans expected, got {type(kmeans).__name__}")
+        self.kmeans = kmeans
+        self._count, self._fed = None, 0
+
+    def feed(self, batch: torch.Tensor) -> None:
+        labels, _ = self.kmeans.assign(batch)
+        if self._count is None:
+            self._count = torch.zeros(self.kmeans.bins, dtype=torch.int64, device=labels.device)
+        km_ops.km_count(labels, self._count)
+        self._fed += labels.shape[0]
+
+    def per_bin(self) -> Dict[str, List]:
+        """{"reference": the K bin counts of the fitted set, "query": those of the fed set, "z": the K z values}; the one copy of
+        2 K integers to the host"""
+        if not self._fed:
+            raise ValueError("no image fed yet")
+        a, b = torch.stack([self.kmeans.counts, self._count]).tolist()
+        return {"reference": a, "query": b, "z": ndb_statistics(a, b)["z"]}
+
+    def result(self) -> Dict[str, float]:
+        per = self.per_bin()
+        st = ndb_statistics(per["reference"], per["query"])
+        return {"ndb": st["ndb"], "jsd": st["jsd"]}
