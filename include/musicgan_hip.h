@@ -792,6 +792,21 @@ int mg_km_update(const float* x, int64_t n, int64_t d, const int32_t* order, con
                  size_t ws_bytes, mg_stream_t stream);
 int mg_km_count(const int32_t* label, int64_t n, int k, int64_t* count, mg_stream_t stream);
 
+/* ---- multi-scale L2 loss with its gradient (csrc/pyrloss.hip, plan: csrc/pyrloss_plan.h): the kernels behind
+ * musicgan_amd/proj_ops.py, networks.PyramidL2 and the latent projector, which the reference does not have (definition: DESIGN.md 4.16).
+ * x, t (n, c, h, w) float32; `levels` L in 1 .. 7, h and w multiples of 2^(L-1); weights: HOST array of L finite floats >= 0, read
+ * before the call returns and passed to the kernels by value.
+ *   d_0 = x - t;  d_{s+1} = AvgPool2d(2)(d_s) in mg_avgpool2_fwd's float32 expression
+ *   loss[i] = sum_s weights[s] / (c h_s w_s) * sum (double)d_s^2 over sample i     (n,) float64; fixed order, no atomics
+ *   grad    = d loss[i] / d x = ((weights[L-1] d_{L-1}, then fmaf(weights[s], d_s, .) for s = L-2 .. 0) * (float)(2 / (c h w)))
+ *             (n, c, h, w) float32, or NULL: the loss alone.  It must not overlap x or t (x and t may be the same buffer).
+ * Two launches on `stream`, nothing read back, capturable.  A sample's loss and gradient depend on that sample alone and have the
+ * same bits in every run and for every split of the batch.  ws: mg_pyramid_l2_ws_bytes (0: the shape is refused) at an 8-byte
+ * boundary, fully written. */
+size_t mg_pyramid_l2_ws_bytes(int n, int c, int h, int w, int levels);
+int mg_pyramid_l2(const float* x, const float* t, int n, int c, int h, int w, int levels, const float* weights, double* loss,
+                  float* grad, void* ws, size_t ws_bytes, mg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

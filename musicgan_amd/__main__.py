@@ -1,5 +1,5 @@
 """`python -m musicgan_amd <mode> ...`: the reference's four sub-commands with its positional names and flags
-(/root/reference/music_gan/__main__.py:11-124) and `evaluate` and `loudness`, which the reference does not have, declared as data and dispatched
+(/root/reference/music_gan/__main__.py:11-124) and `evaluate`, `loudness` and `project`, which the reference does not have, declared as data and dispatched
 lazily (importing `train` pulls in the GPU library, `view_audio` pulls in matplotlib)."""
 import argparse
 import importlib
@@ -97,11 +97,21 @@ _MODES = {
                                     "the codec gives)")),
         (("--true-peak",), dict(dest="true_peak", type=float, default=None, metavar="DBTP",
                                 help="true-peak ceiling of --loudness in dBTP (default -1)")),
+        (("--seed",), dict(type=int, default=None, help="draw the latents from a generator seeded with this (default: unseeded)")),
+        (("--latents",), dict(type=str, default=None, metavar="LATENTS.pt",
+                              help="a latents.pt written by `project`: its windows, joined along time, are the one latent and "
+                                   "sound_0 the one file (-n and -m are not used)")),
+        (("--morph-to",), dict(dest="morph_to", type=str, default=None, metavar="LATENTS.pt",
+                               help="with --latents: a second latents.pt with as many windows; -m files on the arc from the first "
+                                    "to the second (spherical interpolation, window by window), ends included")),
     ], lambda a: (a.output_dir, a.rand_channels, a.gen_dict_state, a.nb_vec, a.nb_music),
         lambda a: {**({"audio_format": a.audio_format} if a.audio_format != "wav" else {}),
                    **({"griffin_lim": a.griffin_lim} if a.griffin_lim else {}),
                    **({"loudness": a.loudness} if a.loudness is not None else {}),
-                   **({"peak_dbtp": a.true_peak} if a.true_peak is not None else {})}),
+                   **({"peak_dbtp": a.true_peak} if a.true_peak is not None else {}),
+                   **({"seed": a.seed} if a.seed is not None else {}),
+                   **({"latents": a.latents} if a.latents is not None else {}),
+                   **({"morph_to": a.morph_to} if a.morph_to is not None else {})}),
     "view_audio": ("view_audio", "view_audio", [
         (("--input-audio",), dict(type=str, required=True)),
         (("--image-idx",), dict(type=int, required=True)),
@@ -137,13 +147,42 @@ _FILE_MODES = {
         (("-o", "--output"), dict(type=str, default=None, help="also write the measurements as JSON to this file")),
     ], lambda a: (a.audio_path,), lambda a: {"output": a.output} if a.output is not None else {}),
 }
+# sub-commands that work on latents (same declaration; kept apart as well)
+_LATENT_MODES = {
+    "project": ("project", "project", [
+        (("gen_dict_state",), dict(type=str)),
+        (("rand_channels",), dict(type=int)),
+        (("audio_path",), dict(type=str, help="the recording to project (any format that can be read: wav, aiff, au, flac, ogg)")),
+        (("-o", "--output-dir"), dict(type=str, required=True, help="receives latents.pt, projection.json and, at level 7, "
+                                                                    "reconstruction.* and target.*")),
+        (("--level",), dict(type=int, default=7, help="growth level of the checkpoint (7: fully grown, 512 x 512)")),
+        (("--steps",), dict(type=int, default=1000, help="Adam steps per window (default 1000, the StyleGAN2 projector's)")),
+        (("--lr",), dict(type=float, default=0.1, help="peak learning rate: linear ramp over the first 5 %% of the steps, cosine "
+                                                       "decay over the last 25 %%")),
+        (("--candidates",), dict(type=int, default=16, help="seeded random latents per window of which the closest is the start")),
+        (("--batch-size",), dict(dest="batch_size", type=int, default=6, help="windows optimised together")),
+        (("--seed",), dict(type=int, default=0)),
+        (("--format",), dict(dest="audio_format", choices=("wav", "flac", "ogg"), default="wav")),
+        (("--griffin-lim",), dict(dest="griffin_lim", type=int, default=0, metavar="N",
+                                  help="N rounds of Griffin-Lim phase refinement before the two audio files are written")),
+        (("--resample",), dict(action="store_true", help="resample a file that is not at 44.1 kHz (else it is refused)")),
+    ], lambda a: (a.gen_dict_state, a.rand_channels, a.audio_path, a.output_dir),
+        lambda a: dict(level=a.level, steps=a.steps, lr=a.lr, candidates=a.candidates, batch_size=a.batch_size, seed=a.seed,
+                       **({"audio_format": a.audio_format} if a.audio_format != "wav" else {}),
+                       **({"griffin_lim": a.griffin_lim} if a.griffin_lim else {}),
+                       **({"resample": True} if a.resample else {}))),
+}
+
+
+def _all_modes() -> dict:
+    return {**_MODES, **_FILE_MODES, **_LATENT_MODES}
 
 
 def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser("MusicGAN")
     modes = parser.add_subparsers(dest="mode")
     modes.required = True
-    for mode, (_, _, arguments, *_) in {**_MODES, **_FILE_MODES}.items():
+    for mode, (_, _, arguments, *_) in _all_modes().items():
         sub = modes.add_parser(mode)
         for flags, kwargs in arguments:
             sub.add_argument(*flags, **kwargs)
@@ -154,7 +193,7 @@ def build_parser() -> argparse.ArgumentParser:
 
 def main(argv=None) -> None:
     args = build_parser().parse_args(argv)
-    module, function, _, call_args, *call_kwargs = {**_MODES, **_FILE_MODES}[args.mode]
+    module, function, _, call_args, *call_kwargs = _all_modes()[args.mode]
     kwargs = call_kwargs[0](args) if call_kwargs else {}
     getattr(importlib.import_module(f".{module}", __package__), function)(*call_args(args), **kwargs)
 

@@ -237,6 +237,8 @@ SIGNATURES = {
     "mg_km_update_ws_bytes": (c_size_t, [c_int64, c_int64, c_int]),
     "mg_km_update": (c_int, [_P, c_int64, c_int64, _P, _P, c_int, _P, _P, c_size_t, _P]),
     "mg_km_count": (c_int, [_P, c_int64, c_int, _P, _P]),
+    "mg_pyramid_l2_ws_bytes": (c_size_t, [c_int] * 5),
+    "mg_pyramid_l2": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), _P, _P, _P, c_size_t, _P]),
 }
 
 _lib = None

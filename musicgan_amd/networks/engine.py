@@ -352,6 +352,19 @@ class GradSink:
         return ops.gen_head_bwd(g_mp, mp, w, p, rn, gw, gb, accumulate=acc, **kw)
 
 
+class DataOnlySink(GradSink):
+    """A backward pass for the data gradient alone (the latent's, with need_gz): the weight-gradient launches of the convolutions,
+    which nobody reads when every parameter is frozen, are left out.  `gen_head` stays: that launch is the data path of a head --
+    the 1x1 data gradient and the PixelNorm / LeakyReLU backward in one pass over p, returning the masked gradient the chain goes on
+    with -- and its 2 x C weight gradient, into a slot nobody reads, is the price of the fusion."""
+
+    def conv3x3(self, w, b, x: torch.Tensor, gy: torch.Tensor, **kw) -> None:
+        pass
+
+    def conv1x1(self, w, b, x: torch.Tensor, gy: torch.Tensor, **kw) -> None:
+        pass
+
+
 # =====================================================================================================================
 # Generator
 # =====================================================================================================================

@@ -32,9 +32,13 @@ class _GenFn(th.autograd.Function):
     @staticmethod
     @th.autograd.function.once_differentiable
     def backward(ctx, g_out):
-        sink = engine.GradSink()
+        # every parameter frozen (a projection step): the data path alone, no weight-gradient launch
+        frozen = not any(ctx.needs_input_grad[3:])
+        sink = engine.DataOnlySink() if frozen else engine.GradSink()
         gz = engine.gen_backward(ctx.W, ctx.saved, g_out, ctx.net._pack_cache, sink, need_gz=ctx.need_gz)
         ctx.saved = None
+        if frozen:
+            return (gz, None, None) + (None,) * len(ctx.W.tensors())
         return (gz, None, None) + tuple(sink.get(p) for p in ctx.W.tensors())
 
 
