@@ -807,6 +807,26 @@ size_t mg_pyramid_l2_ws_bytes(int n, int c, int h, int w, int levels);
 int mg_pyramid_l2(const float* x, const float* t, int n, int c, int h, int w, int levels, const float* weights, double* loss,
                   float* grad, void* ws, size_t ws_bytes, mg_stream_t stream);
 
+/* ---- harmonic / percussive separation and overlap-add re-timing (csrc/hpss.hip): the kernels behind musicgan_amd/hpss_ops.py,
+ * audio.hpss / harmonic / percussive and the transient-preserving time stretch, which the reference does not have (definition:
+ * DESIGN.md 4.17).  x_c64 (512, frames) interleaved complex64 in mg_stft_1024's layout, frames >= 1.
+ *   S = |x| (float32, torch's bits);  Hm[k,t] = median of S[k, t - (lh-1)/2 .. t + (lh-1)/2];  Pm[k,t] = median of
+ *   S[k - (lp-1)/2 .. k + (lp-1)/2, t];  indices past an end reflected (j -> r = j mod 2 n, r < n ? r : 2 n - 1 - r);
+ *   softmask(A, B) = A > B for power = infinity; else with Z = max(A, B): Z < 2^-126 ? (both margins 1 ? 1/2 : 0) :
+ *   (A/Z)^power / ((A/Z)^power + (B/Z)^power);   mask_h = softmask(Hm, margin_h Pm),  mask_p = softmask(Pm, margin_p Hm);
+ *   harm = x mask_h,  perc = x mask_p.
+ * lh, lp odd in [3, 63]; power 1, 2 or INFINITY; margins finite and >= 1.  Each of the six outputs (harm, perc (512, frames)
+ * complex64; H, P, mask_h, mask_p (512, frames) float32) is written when its pointer is given, at least one must be; none may overlap
+ * x.  One launch on `stream`, no workspace, no allocation, no synchronisation, no atomics: capturable.  A median is a selection and
+ * a bin depends on its own windows alone: the same bits in every run, whatever surrounds the windows.
+ * mg_ola_stretch: y[256 m + j] = w[j] xz[a_m + j] + w[j + 256] xz[a_{m-1} + j + 256] for 0 <= j < 256 and 256 m + j < out_length, with
+ *   a_m = floor(256 m p / q) in 64-bit integers, a_{-1} = -256, xz = x inside [0, length) and 0 outside, w[i] = (1 - cos(2 pi i /
+ *   512)) / 2 computed in float64 and rounded once.  p / q in [1/8, 8], length >= 1, out_length >= 0, out_length p < 2^62.  One
+ *   launch, a gather: nothing is accumulated across threads. */
+int mg_hpss(const float* x_c64, float* harm_c64, float* perc_c64, float* H, float* P, float* mask_h, float* mask_p, int64_t frames,
+            int lh, int lp, float power, float margin_h, float margin_p, mg_stream_t stream);
+int mg_ola_stretch(const float* x, int64_t length, float* y, int64_t out_length, int p, int q, mg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,5 @@
 """`python -m musicgan_amd <mode> ...`: the reference's four sub-commands with its positional names and flags
-(/root/reference/music_gan/__main__.py:11-124) and `evaluate`, `loudness` and `project`, which the reference does not have, declared as data and dispatched
+(/root/reference/music_gan/__main__.py:11-124) and `evaluate`, `loudness`, `separate` and `project`, which the reference does not have, declared as data and dispatched
 lazily (importing `train` pulls in the GPU library, `view_audio` pulls in matplotlib)."""
 import argparse
 import importlib
@@ -56,9 +56,17 @@ _MODES = {
                                    "at its own pitch: GPU phase vocoder")),
         (("--pitch",), dict(type=_fraction_list, default=(), metavar="-1,1",
                             help="also write every file transposed by these numbers of semitones at its own duration")),
+        (("--preserve-transients",), dict(dest="preserve_transients", action="store_true",
+                                          help="with --stretch / --pitch: re-time only the harmonic part of every variant with the "
+                                               "phase vocoder and overlap-add its percussive part, so that drum hits stay sharp")),
+        (("--component",), dict(choices=("harmonic", "percussive"), default=None,
+                                help="code only this component of every spectrum (median-filtering harmonic / percussive "
+                                     "separation), the original's and each variant's")),
     ], lambda a: (a.audio_path, a.output_dir),
         lambda a: {**({"resample": True} if a.resample else {}), **({"stretch": a.stretch} if a.stretch else {}),
-                   **({"pitch": a.pitch} if a.pitch else {})}),
+                   **({"pitch": a.pitch} if a.pitch else {}),
+                   **({"preserve_transients": True} if a.preserve_transients else {}),
+                   **({"component": a.component} if a.component is not None else {})}),
     "train": ("train", "train", [
         (("run",), dict(type=str, metavar="RUN_NAME")),
         (("-o", "--out-path"), dict(dest="out_path", type=str, required=True)),
@@ -146,6 +154,20 @@ _FILE_MODES = {
         (("audio_path",), dict(type=str, help="can be /path/to/*.wav (any format that can be read: wav, aiff, au, flac, ogg)")),
         (("-o", "--output"), dict(type=str, default=None, help="also write the measurements as JSON to this file")),
     ], lambda a: (a.audio_path,), lambda a: {"output": a.output} if a.output is not None else {}),
+    "separate": ("separate", "separate", [
+        (("audio_path",), dict(type=str, metavar="AUDIO", help="one recording (any format that can be read: wav, aiff, au, flac, ogg)")),
+        (("-o", "--output-dir"), dict(type=str, required=True, help="receives harmonic.* and percussive.*")),
+        (("--format",), dict(dest="audio_format", choices=("wav", "flac", "ogg"), default="wav")),
+        (("--kernel",), dict(type=int, default=31, metavar="L",
+                             help="length of both median filters, odd, 3 .. 63 (default 31: 0.18 s of frames, 1.3 kHz of bins)")),
+        (("--margin",), dict(type=float, default=1.0, metavar="M",
+                             help="how much larger a component's estimate must be to claim a bin (default 1: the two files sum "
+                                  "to the input; above 1 a residual is left out of both)")),
+        (("--resample",), dict(action="store_true", help="resample a file that is not at 44.1 kHz (else it is refused)")),
+    ], lambda a: (a.audio_path, a.output_dir),
+        lambda a: {**({"audio_format": a.audio_format} if a.audio_format != "wav" else {}),
+                   **({"kernel_size": a.kernel} if a.kernel != 31 else {}), **({"margin": a.margin} if a.margin != 1.0 else {}),
+                   **({"resample": True} if a.resample else {})}),
 }
 # sub-commands that work on latents (same declaration; kept apart as well)
 _LATENT_MODES = {

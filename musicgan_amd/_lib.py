@@ -239,6 +239,8 @@ SIGNATURES = {
     "mg_km_count": (c_int, [_P, c_int64, c_int, _P, _P]),
     "mg_pyramid_l2_ws_bytes": (c_size_t, [c_int] * 5),
     "mg_pyramid_l2": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), _P, _P, _P, c_size_t, _P]),
+    "mg_hpss": (c_int, [_P] * 7 + [c_int64, c_int, c_int, c_float, c_float, c_float, _P]),
+    "mg_ola_stretch": (c_int, [_P, c_int64, _P, c_int64, c_int, c_int, _P]),
 }
 
 _lib = None

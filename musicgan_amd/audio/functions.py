@@ -9,7 +9,7 @@ from typing import Tuple
 import torch as th
 
 from . import constant, wavio
-from .. import gl_ops, loud_ops, ops, pv_ops
+from .. import gl_ops, hpss_ops, loud_ops, ops, pv_ops
 
 _bark_cache = {}
 
@@ -169,14 +169,69 @@ def phase_vocoder(complex_specgrams: th.Tensor, rate) -> th.Tensor:
     return pv_ops.phase_vocoder(complex_specgrams.to(dev, th.complex64).contiguous(), r.numerator, r.denominator)
 
 
-def time_stretch(waveform: th.Tensor, rate) -> th.Tensor:
+def hpss(complex_spec: th.Tensor, kernel_size=31, power: float = 2.0, margin=1.0, mask: bool = False) -> Tuple[th.Tensor, th.Tensor]:
+    """librosa.decompose.hpss for this package's STFT: complex (512, T), T >= 1 -> (harmonic, percussive), two complex64 (512, T)
+    spectra on the device (a CPU tensor is moved there first); with `mask` the two float32 masks instead.  Median filtering
+    (Fitzgerald 2010): the harmonic estimate is the median of |X| along time, the percussive one along frequency, each over
+    kernel_size (an odd int in [3, 63], or a pair (frames, bins)) with reflected ends; the masks are librosa's softmask at `power`
+    (1, 2 or inf) with `margin` (a number >= 1, or a pair (harmonic, percussive)).  With margin 1 the two components sum to the
+    input; above 1 a residual is left out of both."""
+    args = hpss_ops.check_arguments(kernel_size, power, margin, ("mask_h", "mask_p") if mask else ("harmonic", "percussive"))
+    if complex_spec.dim() != 2 or complex_spec.shape[0] != constant.N_FFT // 2 or complex_spec.shape[1] < 1:
+        raise ValueError(f"a ({constant.N_FFT // 2}, T >= 1) spectrum expected, got {tuple(complex_spec.shape)}")
+    if not complex_spec.is_complex():
+        raise ValueError(f"a complex spectrum expected, got {complex_spec.dtype}")
+    dev = complex_spec.device if complex_spec.is_cuda else _device()
+    return hpss_ops.hpss(complex_spec.to(dev, th.complex64).contiguous(), args[:2], args[2], args[3:5], args[5])
+
+
+def _component(waveform: th.Tensor, index: int, kernel_size, power, margin) -> th.Tensor:
+    if waveform.dim() != 1 or not waveform.is_floating_point():
+        raise ValueError(f"a mono floating-point waveform (samples,) expected, got {tuple(waveform.shape)} {waveform.dtype}")
+    hpss_ops.check_arguments(kernel_size, power, margin)
+    return istft(hpss(stft_from_waveform(waveform), kernel_size, power, margin)[index])
+
+
+def harmonic(waveform: th.Tensor, kernel_size=31, power: float = 2.0, margin=1.0) -> th.Tensor:
+    """librosa.effects.harmonic: mono (samples,) float waveform -> its harmonic component, 256 * (samples // 256) samples:
+    `istft(hpss(stft_from_waveform(waveform))[0])`; fewer than 4 frames raise the ValueError of `istft`.  kernel_size, power,
+    margin: as `hpss` takes them."""
+    return _component(waveform, 0, kernel_size, power, margin)
+
+
+def percussive(waveform: th.Tensor, kernel_size=31, power: float = 2.0, margin=1.0) -> th.Tensor:
+    """librosa.effects.percussive: as `harmonic`, the percussive component"""
+    return _component(waveform, 1, kernel_size, power, margin)
+
+
+def time_stretch(waveform: th.Tensor, rate, preserve_transients: bool = False) -> th.Tensor:
     """mono (samples,) float waveform -> the same sound `rate` times as fast at the same pitch: `istft(phase_vocoder(
     stft_from_waveform(waveform), rate))`, 256 * (n - 1) samples for n = ceil((1 + samples // 256) / rate) frames; n < 4 raises
-    the ValueError of `istft`.  rate: as `phase_vocoder` takes it."""
+    the ValueError of `istft`.  rate: as `phase_vocoder` takes it.
+    preserve_transients (Driedger, Mueller, Ewert 2014): the spectrum is split by `hpss`; only the harmonic part goes through the
+    phase vocoder, the percussive part is re-timed by overlap-add of short frames, which copies every hit as it is:
+    `istft(phase_vocoder(Xh, rate)) + ola_stretch(istft(Xp), p, q, 256 * (n - 1))`, the same length; fewer than 4 frames on either
+    side raise the ValueError of `istft`."""
     r = pv_ops.as_rate(rate)
     if waveform.dim() != 1 or not waveform.is_floating_point():
         raise ValueError(f"a mono floating-point waveform (samples,) expected, got {tuple(waveform.shape)} {waveform.dtype}")
-    return istft(phase_vocoder(stft_from_waveform(waveform), r))
+    if not preserve_transients:
+        return istft(phase_vocoder(stft_from_waveform(waveform), r))
+    return retime_preserving_transients(stft_from_waveform(waveform), r, as_waveform=True)
+
+
+def retime_preserving_transients(complex_spec: th.Tensor, rate, as_waveform: bool = False) -> th.Tensor:
+    """complex64 (512, T >= 4) on the device -> the spectrum (512, n = ceil(T / rate)) of the transient-preserving re-timing:
+    `phase_vocoder(Xh, rate) + stft(ola_stretch(istft(Xp), p, q, 256 * (n - 1)))` for (Xh, Xp) = hpss(X); as_waveform: the
+    waveform `istft(phase_vocoder(Xh, rate)) + ola_stretch(...)` of 256 * (n - 1) samples instead (what `time_stretch` returns)."""
+    r = pv_ops.as_rate(rate)
+    xh, xp = hpss(complex_spec)
+    samples = hpss_ops.stretched_samples(complex_spec.shape[1], r)
+    hits = hpss_ops.ola_stretch(istft(xp), r.numerator, r.denominator, samples)
+    tones = phase_vocoder(xh, r)
+    if as_waveform:
+        return istft(tones) + hits
+    return tones + ops.stft_1024(hits)
 
 
 def pitch_ratio(n_steps) -> Fraction:
@@ -187,13 +242,13 @@ def pitch_ratio(n_steps) -> Fraction:
     return Fraction(2 ** (float(n_steps) / 12)).limit_denominator(64)
 
 
-def pitch_shift(waveform: th.Tensor, n_steps, sample_rate: int = constant.SAMPLE_RATE) -> th.Tensor:
+def pitch_shift(waveform: th.Tensor, n_steps, sample_rate: int = constant.SAMPLE_RATE, preserve_transients: bool = False) -> th.Tensor:
     """torchaudio.functional.pitch_shift for a mono (samples,) waveform: with P / Q = pitch_ratio(n_steps), `time_stretch` by Q / P
     (longer for an upward shift), then `resample` from P to Q, cropped or zero-padded to the input's length.  The result does not
-    depend on `sample_rate` (kept for torchaudio's signature)."""
+    depend on `sample_rate` (kept for torchaudio's signature).  preserve_transients: passed to `time_stretch`."""
     f = pitch_ratio(n_steps)
     pv_ops.as_rate(1 / f)
-    y = time_stretch(waveform, 1 / f)
+    y = time_stretch(waveform, 1 / f, preserve_transients=preserve_transients)
     y = resample(y, f.numerator, f.denominator)
     n = waveform.shape[0]
     if y.shape[0] >= n:

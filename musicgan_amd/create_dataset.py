@@ -16,6 +16,10 @@ unchanged path.
 `stretch` / `pitch` add re-timed and transposed copies of every file behind its own samples (audio.phase_vocoder on the file's STFT;
 for a pitch, the mono signal resampled by P / Q first and re-timed by Q / P, which restores the duration): the remedy for a small
 corpus.  Without them nothing changes.
+`preserve_transients` (with `stretch` / `pitch` only) re-times every variant as audio.time_stretch(..., preserve_transients=True)
+does: the harmonic part of the spectrum (audio.hpss) through the phase vocoder, the percussive part by overlap-add, so that drum hits
+are not smeared; the variant has the same number of frames either way.  `component` ("harmonic" or "percussive") replaces every
+spectrum about to be coded, the original's and each variant's, by that component of it.  Without the two nothing changes.
 A single-process run records in the side-car which samples are consecutive chunks of one spectrum ("tracks": a file's own samples
 are one, each variant another): what training with random time offsets (`train --random-offset`) cuts its windows from.
 """
@@ -73,6 +77,20 @@ def check_variants(stretch=(), pitch=()):
     if len({float(v) for v, _ in ratios}) != len(ratios) or len({f for _, f in ratios}) != len(ratios):
         raise ValueError(f"duplicate pitch values: {[str(v) for v, _ in ratios]}")
     return tuple(rates), tuple(ratios)
+
+
+COMPONENTS = ("harmonic", "percussive")
+
+
+def check_separation(component=None, preserve_transients=False, rates=(), ratios=()) -> None:
+    """ValueError for a component other than None / "harmonic" / "percussive" and for preserve_transients without a variant to
+    apply it to -- host arithmetic, no device needed"""
+    if component is not None and component not in COMPONENTS:
+        raise ValueError(f"component must be one of {COMPONENTS} or None, got {component!r}")
+    if not isinstance(preserve_transients, bool):
+        raise ValueError(f"preserve_transients must be True or False, got {preserve_transients!r}")
+    if preserve_transients and not (rates or ratios):
+        raise ValueError("preserve_transients applies to the stretch / pitch variants: give at least one")
 
 
 def variant_counts(nb_frames_wav: int, nb_vec: int, rates=(), ratios=()) -> list:
@@ -332,14 +350,18 @@ class _Chunk:
 
 
 def create_dataset(audio_path: str, dataset_output_dir: str, *, packed: bool = True, writer_threads: int = 0,
-                   stats: dict = None, resample: bool = False, stretch=(), pitch=()) -> None:
+                   stats: dict = None, resample: bool = False, stretch=(), pitch=(), component=None,
+                   preserve_transients: bool = False) -> None:
     """`packed` (extension, single-process runs): also write the float32 memory-mapped side-car the fast loader reads
     (audio/dataset.py); the reference-format `magn_phase_{idx}.pt` files are written either way.  `writer_threads`: 0 = one per
     available CPU (at most 16).  `resample`: files not at 44.1 kHz are resampled to it (else they raise, as in the reference).
     `stretch`: rates (int, Fraction or float, as audio.phase_vocoder takes them; above 1: faster); `pitch`: semitones.  Behind its own
     samples every file also yields, in the order given, those of its STFT re-timed by each rate, then those of its mono 44.1 kHz
-    signal resampled by P / Q = audio.pitch_ratio(value) and re-timed by Q / P."""
+    signal resampled by P / Q = audio.pitch_ratio(value) and re-timed by Q / P.  `preserve_transients`: the variants are re-timed
+    with their percussive part overlap-added instead of going through the phase vocoder (a file of fewer than 4 frames raises
+    audio.istft's ValueError).  `component`: "harmonic" or "percussive", what audio.hpss leaves of every spectrum is coded."""
     rates, ratios = check_variants(stretch, pitch)
+    check_separation(component, preserve_transients, rates, ratios)
     w_p = glob.glob(audio_path)
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:
@@ -427,20 +449,31 @@ def create_dataset(audio_path: str, dataset_output_dir: str, *, packed: bool = T
             spectra = [complex_values]
             if rates or ratios:  # the variants of this file, from the spectrum and the PCM that are on the device already
                 from . import ops, pv_ops
-                spectra += [pv_ops.phase_vocoder(complex_values, r.numerator, r.denominator) for r in rates]
+
+                def retime(spectrum, r):
+                    if not preserve_transients:
+                        return pv_ops.phase_vocoder(spectrum, r.numerator, r.denominator)
+                    if spectrum.size()[1] < 4:
+                        audio.istft(spectrum)  # raises: nothing that short can be separated and overlap-added
+                    if pv_ops.phase_vocoder_len(spectrum.size()[1], r.numerator, r.denominator) - 1 < nb_vec:
+                        return None  # too short for one image: left out below, as the plain variant would be
+                    return audio.functions.retime_preserving_transients(spectrum, r)
+                spectra += [retime(complex_values, r) for r in rates]
                 if ratios:
                     mono = ops.pcm_to_mono(pcm) if sr == audio.SAMPLE_RATE else ops.resample_pcm(pcm, sr, audio.SAMPLE_RATE)
                     del pcm
                     for _, f in ratios:
                         shifted = ops.stft_1024(ops.resample_rows(mono[None, :], f.numerator, f.denominator)[0].contiguous())
-                        spectra.append(pv_ops.phase_vocoder(shifted, f.denominator, f.numerator))
+                        spectra.append(retime(shifted, 1 / f))
                     del mono
             del complex_values
             for v_i, complex_values in enumerate(spectra):
                 # create_dataset.py:41-42 skips files of fewer than nb_vec frames; a file of EXACTLY nb_vec frames has nb_vec - 1 phase
                 # differences, i.e. no complete image either (the reference would write one degenerate (2, 512, 0) tensor for it)
-                if complex_values.size()[1] - 1 < nb_vec:
+                if complex_values is None or complex_values.size()[1] - 1 < nb_vec:
                     continue  # (a variant that is too short is left out in the same way)
+                if component is not None:  # the last step in front of the codec, in the spectral domain
+                    complex_values = audio.hpss(complex_values)[COMPONENTS.index(component)]
                 both = audio.stft_to_stacked_phase_magn(complex_values, nb_vec=nb_vec)  # (S, 2, 512, nb_vec) float32, on the device
                 n_files += v_i == 0
                 tracks.append([idx, int(both.size()[0])])
