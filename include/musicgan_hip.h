@@ -641,6 +641,36 @@ int mg_true_peak(const float* x, int C, int64_t L, int64_t row_stride, const voi
 int mg_loudness_normalize(const float* x, float* out, int64_t n, const double* record, const float* peak, double target,
                           double ceiling, float* gain, mg_stream_t stream);
 
+/* ------------------------------------------------------------------ look-ahead true-peak limiter (csrc/limiter.hip)
+ * One gain curve g [L] for all C <= 8 rows of x (L float32 samples, `row_stride` floats apart) that keeps every sample of x G g at
+ * or under the ceiling c (definition, steps 1 - 6: DESIGN.md).  A = look-ahead in samples, 0 .. 2047; rho in (0, 1) = release
+ * factor per sample; G = pregain[0], one float64 in DEVICE memory, read by the kernels.  `bank`: mg_resample_bank(1, 4, 6, 0.99)
+ * on the device.
+ * mg_limiter_tile: host only; the samples per workgroup of the hold, release and output kernels.
+ * mg_limiter_ws_bytes: host only; one float32 per sample (m), one float64 per tile of L + A positions and one per position (q), each
+ *   part rounded up to 16 bytes, + 16; 0 for bad arguments.
+ * mg_limiter_envelope: m [L] float32 receives max over the channels of max(|x[n]|, |u[4n - 3 .. 4n + 3]|), u = x interpolated 4x by
+ *   the bank with zeros beyond both ends (the values mg_resample_pcm writes, bit for bit; u outside [0, 4 L) does not count).  One
+ *   launch.
+ * mg_limiter: out [C][L] float32 (contiguous) receives float32(double(x) G g), rounded once; gain_out (optional) [L] float64 receives
+ *   g.  r = c / (G m) where G m > c, else 1; h[n] = min r[n .. n + A]; d[n] = max(1 - h[n], rho d[n - 1]) from d = 0 A samples before
+ *   the file, carried along the whole file; g[n] = min(r[n], mean of 1 - d over n - A .. n).  Everything but m is float64.  Five
+ *   launches (envelope, end state of every tile from zero state, the carry along the tiles, the tiles again from their true state,
+ *   window means and output), no atomics, one order for every scan and sum: the same bits on every run.  |out| <= c (1 + 2^-23);
+ *   where G m <= c everywhere g is exactly 1.  L == 0: nothing is launched.  ws 16-byte aligned, pregain and gain_out 8-byte.
+ * mg_limiter_trim: out [n] = float32(double(y [n]) min(1, ceiling / peak[0])), peak the float32 of mg_true_peak on the device.
+ * mg_limiter_pregain: pregain [1] float64 receives prev[0] 10^((target - record[0]) / 20) (prev == NULL: 1), the factor 1 where
+ *   record[0] = -inf; record of mg_loudness_gate, all of it device memory.  One launch of one thread.
+ * Everything runs on `stream`, allocates nothing and synchronises nothing: the calls can be captured in a graph. */
+int mg_limiter_tile(void);
+size_t mg_limiter_ws_bytes(int C, int64_t L, int A);
+int mg_limiter_envelope(const float* x, int C, int64_t L, int64_t row_stride, const void* bank, size_t bank_bytes, float* m,
+                        mg_stream_t stream);
+int mg_limiter(const float* x, int C, int64_t L, int64_t row_stride, const void* bank, size_t bank_bytes, const double* pregain,
+               double ceiling, int A, double rho, float* out, double* gain_out, void* ws, size_t ws_bytes, mg_stream_t stream);
+int mg_limiter_trim(const float* y, float* out, int64_t n, const float* peak, double ceiling, mg_stream_t stream);
+int mg_limiter_pregain(const double* record, double target, const double* prev, double* pregain, mg_stream_t stream);
+
 /* CRC-32 (zip / zlib) of the float64 widening of float32 samples: crc_out[i] = crc32 of the little-endian bytes of
  * x[i*floats_per_sample ...].astype(float64) -- the checksum the zip container of `th.save(sample.to(th.float64))`
  * [create_dataset.py:52-62] stores for its payload, which the reference's writer computes on one host core per sample.

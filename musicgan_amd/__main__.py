@@ -105,6 +105,14 @@ _MODES = {
                                     "the codec gives)")),
         (("--true-peak",), dict(dest="true_peak", type=float, default=None, metavar="DBTP",
                                 help="true-peak ceiling of --loudness in dBTP (default -1)")),
+        (("--limiter",), dict(action="store_true",
+                              help="with --loudness: hold the peaks under the ceiling with a look-ahead true-peak limiter, so that "
+                                   "a file with a high crest factor reaches the target too (default: one gain, lowered until the "
+                                   "peak fits)")),
+        (("--limiter-attack",), dict(dest="limiter_attack", type=float, default=None, metavar="MS",
+                                     help="look-ahead of --limiter in ms (default 5)")),
+        (("--limiter-release",), dict(dest="limiter_release", type=float, default=None, metavar="MS",
+                                      help="release time of --limiter in ms (default 50)")),
         (("--seed",), dict(type=int, default=None, help="draw the latents from a generator seeded with this (default: unseeded)")),
         (("--latents",), dict(type=str, default=None, metavar="LATENTS.pt",
                               help="a latents.pt written by `project`: its windows, joined along time, are the one latent and "
@@ -117,6 +125,9 @@ _MODES = {
                    **({"griffin_lim": a.griffin_lim} if a.griffin_lim else {}),
                    **({"loudness": a.loudness} if a.loudness is not None else {}),
                    **({"peak_dbtp": a.true_peak} if a.true_peak is not None else {}),
+                   **({"limiter": True} if a.limiter else {}),
+                   **({"limiter_attack": a.limiter_attack} if a.limiter_attack is not None else {}),
+                   **({"limiter_release": a.limiter_release} if a.limiter_release is not None else {}),
                    **({"seed": a.seed} if a.seed is not None else {}),
                    **({"latents": a.latents} if a.latents is not None else {}),
                    **({"morph_to": a.morph_to} if a.morph_to is not None else {})}),
@@ -214,7 +225,11 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def main(argv=None) -> None:
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.mode == "generate" and args.loudness is None and (
+            args.limiter or args.limiter_attack is not None or args.limiter_release is not None):
+        parser.error("--limiter, --limiter-attack and --limiter-release need --loudness")
     module, function, _, call_args, *call_kwargs = _all_modes()[args.mode]
     kwargs = call_kwargs[0](args) if call_kwargs else {}
     getattr(importlib.import_module(f".{module}", __package__), function)(*call_args(args), **kwargs)

@@ -206,6 +206,13 @@ SIGNATURES = {
     "mg_true_peak_ws_bytes": (c_size_t, [c_int, c_int64]),
     "mg_true_peak": (c_int, [_P, c_int, c_int64, c_int64, _P, c_size_t, _P, _P, c_size_t, _P]),
     "mg_loudness_normalize": (c_int, [_P, _P, c_int64, _P, _P, ctypes.c_double, ctypes.c_double, _P, _P]),
+    "mg_limiter_tile": (c_int, []),
+    "mg_limiter_ws_bytes": (c_size_t, [c_int, c_int64, c_int]),
+    "mg_limiter_envelope": (c_int, [_P, c_int, c_int64, c_int64, _P, c_size_t, _P, _P]),
+    "mg_limiter": (c_int, [_P, c_int, c_int64, c_int64, _P, c_size_t, _P, ctypes.c_double, c_int, ctypes.c_double, _P, _P, _P, c_size_t,
+                           _P]),
+    "mg_limiter_trim": (c_int, [_P, _P, c_int64, _P, ctypes.c_double, _P]),
+    "mg_limiter_pregain": (c_int, [_P, ctypes.c_double, _P, _P, _P]),
     "mg_swd_pyr_down": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "mg_swd_pyr_lap": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     "mg_swd_gather": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64, _P]),

@@ -4,12 +4,13 @@
 from __future__ import annotations
 
 from fractions import Fraction
+import math
 from typing import Tuple
 
 import torch as th
 
 from . import constant, wavio
-from .. import gl_ops, hpss_ops, loud_ops, ops, pv_ops
+from .. import gl_ops, hpss_ops, lim_ops, loud_ops, ops, pv_ops
 
 _bark_cache = {}
 
@@ -321,45 +322,122 @@ def true_peak(waveform: th.Tensor) -> th.Tensor:
     return loud_ops.true_peak(_loudness_input(waveform, min_length=1))
 
 
+def limit(waveform: th.Tensor, sample_rate: int, ceiling_dbtp: float = -1.0, gain_db: float = 0.0, attack_ms: float = 5.0,
+          release_ms: float = 50.0, return_gain: bool = False):
+    """Look-ahead true-peak limiter: waveform * 10^(gain_db / 20) * g in float32 on the device, in the waveform's shape ((L,) or
+    (C <= 8, L); a CPU tensor is moved there first), with one gain curve g <= 1 for all channels, so that the stereo image does not
+    move.  g holds every sample and the seven points of the 4x interpolation around it at or under 10^(ceiling_dbtp / 20) where they
+    are scaled by that sample's gain: it looks attack_ms ahead (5 ms; round(attack_ms fs / 1000) samples, 0 .. 2047), falls over
+    that time as the mean of a held minimum and recovers by the factor exp(-1 / (release_ms fs / 1000)) per sample (DESIGN.md,
+    "True-peak limiter").  No sample of the result exceeds the ceiling; where nothing reaches it the result is waveform * gain
+    exactly.  return_gain: also g, a float64 (L,) tensor on the device."""
+    ceiling, lookahead, rho = lim_ops.check_arguments(sample_rate, ceiling_dbtp, attack_ms, release_ms)
+    gain = 10.0 ** (lim_ops._number("gain_db", gain_db) / 20.0)
+    x = _loudness_input(waveform)
+    pregain = th.full((1,), gain, dtype=th.float64, device=x.device)
+    out = lim_ops.limit(x, pregain, ceiling, lookahead, rho, return_gain=return_gain)
+    if return_gain:
+        return out[0].reshape(waveform.shape), out[1]
+    return out.reshape(waveform.shape)
+
+
+def _db20(v: th.Tensor) -> th.Tensor:
+    return 20.0 * th.log10(v.to(th.float64))
+
+
 def normalize_loudness(waveform: th.Tensor, sample_rate: int, target_lufs: float = -14.0, peak_dbtp: float = -1.0,
-                       return_gain: bool = False):
+                       return_gain: bool = False, limiter: bool = False, attack_ms: float = 5.0, release_ms: float = 50.0,
+                       passes: int = 2, return_details: bool = False):
     """waveform * gain in float32 on the device, in the waveform's shape, with one gain for all channels:
     gain = min(10^((target_lufs - loudness) / 20), 10^(peak_dbtp / 20) / true_peak) -- the target loudness unless the true-peak
     ceiling binds first; 1 where the loudness is -inf.  The gain is computed in float64 on the device, rounded once to float32 and
-    never visits the host.  return_gain: also the gain, a float32 0-dim tensor on the device."""
+    never visits the host.  return_gain: also the gain, a float32 0-dim tensor on the device.
+    limiter: the peaks that the target's gain would push past the ceiling are held under it by `limit` (attack_ms, release_ms)
+    instead of lowering the whole file: y = limit(waveform, G) with G = 10^((target_lufs - loudness) / 20), `passes` times (1 .. 4),
+    G multiplied before every pass but the first by 10^((target_lufs - loudness(y)) / 20) -- limiting lowers the loudness, and this
+    hands the loss back -- then y * min(1, ceiling / true_peak(y)), so that the ceiling holds as `true_peak` measures it.  A fixed
+    number of passes, every scalar on the device; the gain returned is the last G times that trim, float32.
+    return_details: also (loudness in LUFS, true peak in dBTP, largest gain reduction of the limiter in dB) of the result, float64
+    0-dim tensors on the device (the reduction is 0 without the limiter): the loudness reached is reported, not promised."""
     loud_ops.check_sample_rate(sample_rate)
     loud_ops.check_targets(target_lufs, peak_dbtp)
+    if limiter:
+        ceiling, lookahead, rho = lim_ops.check_arguments(sample_rate, peak_dbtp, attack_ms, release_ms)
+        lim_ops.check_passes(passes)
     x = _loudness_input(waveform)
+    reduction = th.zeros((), dtype=th.float64, device=x.device) if return_details else None
     if x.shape[1] < 1:
         out, gain = x.clone(), th.ones((), dtype=th.float32, device=x.device)
-    else:
+    elif not limiter:
         x = x.contiguous()
         record = loud_ops.gate(loud_ops.segment_energies(x, sample_rate), sample_rate)
         out, gain = loud_ops.normalize(x, record, loud_ops.true_peak(x), target_lufs, peak_dbtp)
+    else:
+        x = x.contiguous()
+        pregain = lim_ops.pregain(loud_ops.gate(loud_ops.segment_energies(x, sample_rate), sample_rate), target_lufs)
+        for i in range(passes):
+            if i > 0:
+                record = loud_ops.gate(loud_ops.segment_energies(y, sample_rate), sample_rate)
+                pregain = lim_ops.pregain(record, target_lufs, prev=pregain)
+            want_curve = return_details and i == passes - 1
+            y = lim_ops.limit(x, pregain, ceiling, lookahead, rho, return_gain=want_curve)
+            if want_curve:
+                y, curve = y
+                reduction = -_db20(curve.min())
+        peak = loud_ops.true_peak(y)
+        out = lim_ops.trim(y, peak, ceiling)
+        gain = (pregain[0] * th.clamp(ceiling / peak.to(th.float64), max=1.0)).to(th.float32) if return_gain else None
     out = out.reshape(waveform.shape)
-    return (out, gain) if return_gain else out
+    result = (out, gain) if return_gain else (out,)
+    if return_details:
+        if out.numel() and x.shape[1] >= 1:
+            flat = out.reshape(x.shape)
+            lufs = loud_ops.gate(loud_ops.segment_energies(flat, sample_rate), sample_rate)[0]
+            details = (lufs, _db20(loud_ops.true_peak(flat)), reduction)
+        else:
+            ninf = th.full((), -math.inf, dtype=th.float64, device=x.device)
+            details = (ninf, ninf.clone(), reduction)
+        result = result + (details,)
+    return result if len(result) > 1 else out
+
+
+def _limiter_keywords(loudness, limiter, attack_ms, release_ms, sample_rate, peak_dbtp) -> dict:
+    """the limiter's keywords for `normalize_loudness`, checked; empty without the limiter"""
+    if not limiter:
+        return {}
+    if loudness is None:
+        raise ValueError("limiter needs loudness: it holds the peaks that the gain to a loudness target pushes past the ceiling")
+    lim_ops.check_arguments(sample_rate, peak_dbtp, attack_ms, release_ms)
+    return {"limiter": True, "attack_ms": attack_ms, "release_ms": release_ms}
 
 
 def magn_phase_to_waveform(magn_phase: th.Tensor, griffin_lim: int = 0, momentum: float = 0.99, loudness=None,
-                           peak_dbtp: float = -1.0, sample_rate: int = constant.SAMPLE_RATE) -> th.Tensor:
+                           peak_dbtp: float = -1.0, sample_rate: int = constant.SAMPLE_RATE, limiter: bool = False,
+                           attack_ms: float = 5.0, release_ms: float = 50.0) -> th.Tensor:
     """griffin_lim: rounds of Griffin-Lim phase refinement from the decoded phase (0: none, the reference's single inversion);
     loudness: the integrated loudness in LUFS to bring the waveform to, under the true-peak ceiling peak_dbtp (None: the level the
-    codec gives, as the reference), measured at `sample_rate`"""
+    codec gives, as the reference), measured at `sample_rate`; limiter: hold the peaks under the ceiling with the look-ahead limiter
+    (attack_ms, release_ms: as `limit`) instead of lowering the whole file when the ceiling binds -- needs `loudness`"""
     _check_magn_phase(magn_phase)
     if loudness is not None:
         loud_ops.check_targets(loudness, peak_dbtp)
+    extra = _limiter_keywords(loudness, limiter, attack_ms, release_ms, sample_rate, peak_dbtp)
     if griffin_lim:
         wav = _griffin_lim(magn_phase, n_iter=griffin_lim, momentum=momentum)
     else:
         dev = magn_phase.device if magn_phase.is_cuda else _device()
         mp = magn_phase.to(dev, th.float32).contiguous()
         wav = ops.codec_inv(mp, _bark_vector(constant.N_FFT // 2, dev))
-    return wav if loudness is None else normalize_loudness(wav, sample_rate, loudness, peak_dbtp)
+    return wav if loudness is None else normalize_loudness(wav, sample_rate, loudness, peak_dbtp, **extra)
 
 
 def magn_phase_to_wav(magn_phase: th.Tensor, wav_path: str, sample_rate: int, griffin_lim: int = 0, momentum: float = 0.99,
-                      loudness=None, peak_dbtp: float = -1.0):
-    """loudness / peak_dbtp: as `magn_phase_to_waveform`; the file is normalised after Griffin-Lim and before the writer"""
+                      loudness=None, peak_dbtp: float = -1.0, limiter: bool = False, attack_ms: float = 5.0,
+                      release_ms: float = 50.0):
+    """loudness / peak_dbtp / limiter / attack_ms / release_ms: as `magn_phase_to_waveform`; the file is normalised after
+    Griffin-Lim and before the writer"""
     extra = {} if loudness is None else {"loudness": loudness, "peak_dbtp": peak_dbtp, "sample_rate": sample_rate}
+    if limiter:
+        extra.update(limiter=True, attack_ms=attack_ms, release_ms=release_ms)
     raw_audio = magn_phase_to_waveform(magn_phase, griffin_lim=griffin_lim, momentum=momentum, **extra)
     wavio.save(wav_path, raw_audio[None, :], sample_rate)

@@ -41,11 +41,13 @@ def _given_latents(latents, morph_to, rand_channels: int, nb_music: int):
 
 def generate(output_dir: str, rand_channels: int, gen_dict_state: str, nb_vec: int, nb_music: int,
              audio_format: str = "wav", griffin_lim: int = 0, loudness=None, peak_dbtp: float = -1.0,
-             latents=None, morph_to=None, seed=None) -> None:
+             latents=None, morph_to=None, seed=None, limiter: bool = False, limiter_attack: float = 5.0,
+             limiter_release: float = 50.0) -> None:
     """audio_format: "wav" (32-bit float, the reference's output), "flac" (24-bit) or "ogg" (Ogg Vorbis at the default quality),
     the last two encoded on the GPU; griffin_lim: rounds of Griffin-Lim phase refinement before the file is written (0: none);
     loudness: bring every file to this integrated loudness in LUFS (ITU-R BS.1770-4) under the true-peak ceiling peak_dbtp in dBTP
-    (None: the level the codec gives); seed: the latents come from a device generator seeded with it (None: the global generator's
+    (None: the level the codec gives); limiter: with `loudness`, hold the peaks under the ceiling with the look-ahead true-peak limiter
+    (limiter_attack, limiter_release in ms: audio.limit) instead of delivering a file below the target when the ceiling binds; seed: the latents come from a device generator seeded with it (None: the global generator's
     next draw, as ever); latents: a `latents.pt` written by `project` -- its N windows, side by side along time, are the one latent
     and `sound_0` the one file (nb_vec and nb_music are not used); morph_to: a second such file with as many windows -- nb_music
     files, file i at t = i / (nb_music - 1) of the arc from the first file's latents to the second's, window by window
@@ -54,6 +56,11 @@ def generate(output_dir: str, rand_channels: int, gen_dict_state: str, nb_vec: i
     if loudness is not None:
         from . import loud_ops
         loud_ops.check_targets(loudness, peak_dbtp)
+    if limiter:
+        from . import lim_ops
+        if loudness is None:
+            raise ValueError("limiter needs loudness: it holds the peaks that the gain to a loudness target pushes past the ceiling")
+        lim_ops.check_arguments(audio.SAMPLE_RATE, peak_dbtp, limiter_attack, limiter_release)
     if isinstance(griffin_lim, bool) or not isinstance(griffin_lim, int) or griffin_lim < 0:
         raise ValueError(f"griffin_lim must be a non-negative integer, got {griffin_lim!r}")
     if audio_format not in ("wav", "flac", "ogg"):
@@ -81,4 +88,6 @@ def generate(output_dir: str, rand_channels: int, gen_dict_state: str, nb_vec: i
             image = gen(z.contiguous(), 1.0)
             audio.magn_phase_to_wav(image, os.path.join(output_dir, f"sound_{idx}.{audio_format}"), audio.SAMPLE_RATE,
                                     **({"griffin_lim": griffin_lim} if griffin_lim else {}),
-                                    **({"loudness": loudness, "peak_dbtp": peak_dbtp} if loudness is not None else {}))
+                                    **({"loudness": loudness, "peak_dbtp": peak_dbtp} if loudness is not None else {}),
+                                    **({"limiter": True, "attack_ms": limiter_attack, "release_ms": limiter_release}
+                                       if limiter else {}))
