@@ -38,6 +38,160 @@ def _ndb_bins(half: int) -> int:
     return min(_NDB_BINS, max(2, half // _NDB_PER_BIN))
 
 
+class _Images:
+    """Where every metric draws its images from: `dataset` entries brought to `side` by the training loop's own input transform, and
+    the generator's samples of rows of `latents`.  Which rows share a batch is up to the caller, and is part of the result: the
+    generator's kernels are chosen by the batch size."""
+
+    def __init__(self, dataset, gen, latents: torch.Tensor, side: int, batch_size: int) -> None:
+        self.dataset, self.gen, self.latents, self.device = dataset, gen, latents, latents.device
+        self.side, self.cside, self.batch_size = side, min(side, _NN_SIDE), batch_size
+
+    def real(self, indices) -> torch.Tensor:
+        return ops.input_transform(torch.stack([self.dataset[i] for i in indices]).to(self.device).contiguous(), self.side)
+
+    def fake(self, rows) -> torch.Tensor:
+        """`rows`: a slice, or a list of row numbers"""
+        if not isinstance(rows, slice):
+            rows = torch.tensor(rows, device=self.device)
+        with torch.no_grad():
+            return self.gen(self.latents[rows].contiguous(), 1.0).contiguous()
+
+    def reduced(self, x: torch.Tensor) -> torch.Tensor:
+        """at most _NN_SIDE pixels a side, by 2 x 2 means"""
+        while x.shape[-1] > self.cside:
+            x = ops.avgpool2_fwd(x)
+        return x
+
+    def batches(self, n: int):
+        """(lo, hi) of the batches that make up 0 .. n"""
+        for lo in range(0, n, self.batch_size):
+            yield lo, min(lo + self.batch_size, n)
+
+
+def _check_resident(images: _Images, count: int, what: str) -> None:
+    need, free = count * 2 * images.cside * images.cside * 4, torch.cuda.mem_get_info(images.device)[0]
+    if need > 0.75 * free:
+        raise ValueError(f"{what} images of {images.cside} x {images.cside} resident: {need} bytes, more than three quarters of the "
+                         f"{free} bytes free on the device")
+
+
+# One runner per metric: (images, nb_images, perm, seed) -> its keys of the result, in order; it prints its own lines.  `perm` is one
+# seeded order of the dataset, shared by all.
+def _swd(images: _Images, nb_images: int, perm, seed: int) -> Dict[str, float]:
+    swd = SWD(images.side, images.side, channels=2, images=nb_images, seed=seed)
+    for lo, hi in images.batches(nb_images):
+        swd.feed_real(images.real(range(lo, hi)))
+        swd.feed_fake(images.fake(slice(lo, hi)))
+    result = swd.result()
+    for name, value in result.items():
+        print(f"SWD x 1e3 [{name:>3}] = {value:.4f}")
+    return result
+
+
+def _msssim(images: _Images, nb_images: int, perm, seed: int) -> Dict[str, float]:
+    # random pairs, the same index pairs for both sets: consecutive dataset samples are adjacent chunks of one track, and
+    # pairing neighbours would inflate the real number
+    half = nb_images // 2
+    first, second = perm[:half], perm[half:2 * half]
+    ms_real, ms_fake = (MSSSIM(images.side, images.side, channels=2, pairs=half) for _ in range(2))
+    for lo, hi in images.batches(half):
+        ia, ib = first[lo:hi], second[lo:hi]
+        ms_real.feed(images.real(ia), images.real(ib))
+        ms_fake.feed(images.fake(ia), images.fake(ib))
+    result = {"msssim_real": ms_real.result(), "msssim_fake": ms_fake.result()}
+    for name in result:
+        print(f"MS-SSIM [{name[7:]}] = {result[name]:.6f}")
+    return result
+
+
+def _nn(images: _Images, nb_images: int, perm, seed: int) -> Dict[str, float]:
+    nq, cside = min(nb_images, _NN_QUERIES), images.cside
+    fake_q = torch.cat([images.reduced(images.fake(slice(lo, lo + images.batch_size)))   # whole batches, cut to nq afterwards
+                        for lo, _ in images.batches(nq)])[:nq].contiguous()
+    real_q = torch.cat([images.reduced(images.real(perm[lo:hi])) for lo, hi in images.batches(nq)])
+    nn_fake = NearestNeighbours(fake_q, k=_NN_K)
+    nn_real = NearestNeighbours(real_q, k=_NN_K, query_ids=perm[:nq])   # a real query does not match itself
+    for lo, hi in images.batches(nb_images):
+        ids = list(range(lo, hi))
+        real = images.reduced(images.real(ids))
+        nn_fake.feed(real, ids)
+        nn_real.feed(real, ids)
+    comps = fake_q[0].numel()
+    rms = {name: (nn.result()[0][:, 0].cpu() / comps).sqrt() for name, nn in (("fake", nn_fake), ("real", nn_real))}
+    result = {}
+    for suffix, fn in (("", torch.mean), ("_min", torch.min)):
+        for name in ("fake", "real"):
+            result[f"nn_{name}{suffix}"] = float(fn(rms[name]))
+    for name in ("fake", "real"):
+        print(f"NN RMS [{name}] = {result['nn_' + name]:.6f} (smallest {result['nn_' + name + '_min']:.6f}) at {cside} x {cside}")
+    print("NN: fake well below real, or a smallest fake value near 0, means memorised training samples")
+    return result
+
+
+def _prdc(images: _Images, nb_images: int, perm, seed: int) -> Dict[str, float]:
+    _check_resident(images, 2 * nb_images, f"prdc keeps {nb_images} real and {nb_images} generated")
+    half, cside = nb_images // 2, images.cside
+    prdc = PRDC(k=_PRDC_K)
+    for lo, hi in images.batches(nb_images):
+        prdc.feed_real(images.reduced(images.real(range(lo, hi))))
+        prdc.feed_fake(images.reduced(images.fake(slice(lo, hi))))
+    result = prdc.result()
+    prdc = PRDC(k=_PRDC_K)   # the data against itself: two disjoint random halves (the first pair of sets is released)
+    for lo, hi in images.batches(half):
+        prdc.feed_real(images.reduced(images.real(perm[lo:hi])))
+        prdc.feed_fake(images.reduced(images.real(perm[half + lo:half + hi])))
+    result.update({name + "_real": value for name, value in prdc.result().items()})
+    for name in result:
+        print(f"PRDC [{name:>14}] = {result[name]:.6f} at {cside} x {cside}, k = {_PRDC_K}")
+    print("PRDC: low precision means samples off the data manifold, low recall or coverage means modes missing; compare with "
+          "the _real column (two halves of the data against each other)")
+    return result
+
+
+def _ndb(images: _Images, nb_images: int, perm, seed: int) -> Dict[str, float]:
+    half, cside = nb_images // 2, images.cside
+    bins = _ndb_bins(half)
+    _check_resident(images, half, f"ndb keeps {half} real")
+    km = KMeans(bins, iterations=_NDB_ITERATIONS, seed=seed)   # the bins: fitted on one random half of the real set
+    for lo, hi in images.batches(half):
+        km.feed(images.reduced(images.real(perm[lo:hi])))
+    km.fit()
+    ndb_fake, ndb_real = NDB(km), NDB(km)   # both query sets have `half` images: the z-test's power depends on the size
+    for lo, hi in images.batches(half):
+        ndb_fake.feed(images.reduced(images.fake(slice(lo, hi))))
+        ndb_real.feed(images.reduced(images.real(perm[half + lo:half + hi])))
+    result = ndb_fake.result()
+    result.update({name + "_real": value for name, value in ndb_real.result().items()})
+    last = int(km.changed[-1])
+    print(f"NDB: {bins} k-means bins fitted on {half} real images at {cside} x {cside}; the last of {_NDB_ITERATIONS} iterations "
+          f"changed {last} labels" + ("" if last == 0 else " (not converged: raise the iterations)"))
+    if half < _NDB_PER_BIN * bins:
+        print(f"NDB: fewer than {_NDB_PER_BIN} reference images per bin: the test has little power")
+    for suffix in ("", "_real"):
+        print(f"NDB [{'ndb' + suffix:>8}] = {result['ndb' + suffix]:.6f}, JSD [{'jsd' + suffix:>8}] = {result['jsd' + suffix]:.6f}")
+    print("NDB: ndb well above ndb_real means the samples are spread over the corpus differently from the data: modes missing or "
+          "over-produced; ndb_real is about 0.05 for a held-out half")
+    return result
+
+
+# metric: (its runner, the fewest images it works on, how it refuses fewer); nb_images >= 1 always holds
+_RUNNERS = {
+    "swd": (_swd, 1, None),
+    "msssim": (_msssim, 2, "MS-SSIM needs at least 2 images to pair"),
+    "nn": (_nn, 2, "nearest neighbours need at least 2 images (a real query may not match itself)"),
+    "prdc": (_prdc, 2 * (_PRDC_K + 1), f"prdc needs at least {2 * (_PRDC_K + 1)} images (two halves of k + 1 = {_PRDC_K + 1})"),
+    "ndb": (_ndb, _NDB_MIN_IMAGES, f"ndb needs at least {_NDB_MIN_IMAGES} images (two halves, two bins of two in each)"),
+}
+assert tuple(_RUNNERS) == METRICS_EVERY
+
+
+def _check_sizes(metrics: Sequence[str], nb_images: int) -> None:
+    for name, (_, least, refusal) in _RUNNERS.items():
+        if name in metrics and nb_images < least:
+            raise ValueError(f"{refusal}, got {nb_images}")
+
+
 def evaluate(gen_dict_state: str, rand_channels: int, input_dataset: str, metrics: Sequence[str] = ("swd",), *,
              level: int = _FINAL_LEVEL, nb_images: int = 8192, batch_size: int = 16, seed: int = 0,
              output: Optional[str] = None) -> Dict[str, float]:
@@ -74,10 +228,7 @@ def evaluate(gen_dict_state: str, rand_channels: int, input_dataset: str, metric
     metrics = tuple(metrics)
     if not metrics or any(m not in METRICS_EVERY for m in metrics) or len(set(metrics)) != len(metrics):
         raise ValueError(f"metrics: a non-empty subset of {METRICS_EVERY} expected, got {metrics}")
-    if "prdc" in metrics and nb_images < 2 * (_PRDC_K + 1):
-        raise ValueError(f"prdc needs at least {2 * (_PRDC_K + 1)} images (two halves of k + 1 = {_PRDC_K + 1}), got {nb_images}")
-    if "ndb" in metrics and nb_images < _NDB_MIN_IMAGES:
-        raise ValueError(f"ndb needs at least {_NDB_MIN_IMAGES} images (two halves, two bins of two in each), got {nb_images}")
+    _check_sizes(metrics, nb_images)   # before any work ...
     side = _FULL_SIDE >> (_FINAL_LEVEL - level)
     device = torch.device("cuda", torch.cuda.current_device())
 
@@ -90,136 +241,18 @@ def evaluate(gen_dict_state: str, rand_channels: int, input_dataset: str, metric
     if nb_images > len(dataset):
         print(f"The dataset holds {len(dataset)} samples: evaluating on {len(dataset)} images instead of {nb_images}")
         nb_images = len(dataset)
-    if "msssim" in metrics and nb_images < 2:
-        raise ValueError(f"MS-SSIM needs at least 2 images to pair, got {nb_images}")
-    if "nn" in metrics and nb_images < 2:
-        raise ValueError(f"nearest neighbours need at least 2 images (a real query may not match itself), got {nb_images}")
-    if "prdc" in metrics and nb_images < 2 * (_PRDC_K + 1):
-        raise ValueError(f"prdc needs at least {2 * (_PRDC_K + 1)} images (two halves of k + 1 = {_PRDC_K + 1}), got {nb_images}")
-    if "ndb" in metrics and nb_images < _NDB_MIN_IMAGES:
-        raise ValueError(f"ndb needs at least {_NDB_MIN_IMAGES} images (two halves, two bins of two in each), got {nb_images}")
+    _check_sizes(metrics, nb_images)   # ... and for what the dataset holds
 
     print(f"Evaluate {nb_images} real and {nb_images} generated images of {side} x {side}...")
     rng = torch.Generator(device=device).manual_seed(seed)
     # every latent in one draw (a few MB): the samples do not depend on the batch size
     latents = torch.randn(nb_images, rand_channels, _LATENT_H, _LATENT_W, device=device, generator=rng)
+    perm = torch.randperm(nb_images, generator=torch.Generator().manual_seed(seed)).tolist()
+    images = _Images(dataset, gen, latents, side, batch_size)
     result = {}
-    if "swd" in metrics:
-        swd = SWD(side, side, channels=2, images=nb_images, seed=seed)
-        with torch.no_grad():
-            for lo in range(0, nb_images, batch_size):
-                n = min(batch_size, nb_images - lo)
-                real = torch.stack([dataset[i] for i in range(lo, lo + n)]).to(device)
-                swd.feed_real(ops.input_transform(real.contiguous(), side))
-                swd.feed_fake(gen(latents[lo:lo + n].contiguous(), 1.0).contiguous())
-        result.update(swd.result())
-        for name, value in result.items():
-            print(f"SWD x 1e3 [{name:>3}] = {value:.4f}")
-    if any(m in metrics for m in ("msssim", "nn", "prdc", "ndb")):   # one seeded order of the dataset, shared by all four
-        perm = torch.randperm(nb_images, generator=torch.Generator().manual_seed(seed)).tolist()
-    if "msssim" in metrics:
-        # random pairs, the same index pairs for both sets: consecutive dataset samples are adjacent chunks of one track, and
-        # pairing neighbours would inflate the real number
-        half = nb_images // 2
-        first, second = perm[:half], perm[half:2 * half]
-        ms_real, ms_fake = (MSSSIM(side, side, channels=2, pairs=half) for _ in range(2))
-
-        def real_images(idx):
-            return ops.input_transform(torch.stack([dataset[i] for i in idx]).to(device).contiguous(), side)
-
-        def fake_images(idx):
-            return gen(latents[torch.tensor(idx, device=device)].contiguous(), 1.0).contiguous()
-
-        with torch.no_grad():
-            for lo in range(0, half, batch_size):
-                ia, ib = first[lo:lo + batch_size], second[lo:lo + batch_size]
-                ms_real.feed(real_images(ia), real_images(ib))
-                ms_fake.feed(fake_images(ia), fake_images(ib))
-        result["msssim_real"], result["msssim_fake"] = ms_real.result(), ms_fake.result()
-        for name in ("msssim_real", "msssim_fake"):
-            print(f"MS-SSIM [{name[7:]}] = {result[name]:.6f}")
-    if "nn" in metrics or "prdc" in metrics or "ndb" in metrics:   # all compare images reduced to at most _NN_SIDE pixels a side
-        cside = min(side, _NN_SIDE)
-
-        def reduced(x):
-            while x.shape[-1] > cside:
-                x = ops.avgpool2_fwd(x)
-            return x
-
-        def real_at(idx):
-            return reduced(ops.input_transform(torch.stack([dataset[i] for i in idx]).to(device).contiguous(), side))
-
-    if "nn" in metrics:
-        nq = min(nb_images, _NN_QUERIES)
-        with torch.no_grad():
-            fake_q = torch.cat([reduced(gen(latents[lo:lo + batch_size].contiguous(), 1.0).contiguous())
-                                for lo in range(0, nq, batch_size)])[:nq].contiguous()
-            real_q = torch.cat([real_at(perm[lo:min(lo + batch_size, nq)]) for lo in range(0, nq, batch_size)])
-            nn_fake = NearestNeighbours(fake_q, k=_NN_K)
-            nn_real = NearestNeighbours(real_q, k=_NN_K, query_ids=perm[:nq])   # a real query does not match itself
-            for lo in range(0, nb_images, batch_size):
-                ids = list(range(lo, min(lo + batch_size, nb_images)))
-                real = real_at(ids)
-                nn_fake.feed(real, ids)
-                nn_real.feed(real, ids)
-        comps = fake_q[0].numel()
-        rms = {name: (nn.result()[0][:, 0].cpu() / comps).sqrt() for name, nn in (("fake", nn_fake), ("real", nn_real))}
-        for suffix, fn in (("", torch.mean), ("_min", torch.min)):
-            for name in ("fake", "real"):
-                result[f"nn_{name}{suffix}"] = float(fn(rms[name]))
-        for name in ("fake", "real"):
-            print(f"NN RMS [{name}] = {result['nn_' + name]:.6f} (smallest {result['nn_' + name + '_min']:.6f}) at {cside} x {cside}")
-        print("NN: fake well below real, or a smallest fake value near 0, means memorised training samples")
-    if "prdc" in metrics:
-        need, free = 2 * nb_images * 2 * cside * cside * 4, torch.cuda.mem_get_info(device)[0]
-        if need > 0.75 * free:
-            raise ValueError(f"prdc keeps {nb_images} real and {nb_images} generated images of {cside} x {cside} resident: {need} "
-                             f"bytes, more than three quarters of the {free} bytes free on the device")
-        half = nb_images // 2
-        with torch.no_grad():
-            prdc = PRDC(k=_PRDC_K)
-            for lo in range(0, nb_images, batch_size):
-                prdc.feed_real(real_at(list(range(lo, min(lo + batch_size, nb_images)))))
-                prdc.feed_fake(reduced(gen(latents[lo:lo + batch_size].contiguous(), 1.0).contiguous()))
-            result.update(prdc.result())
-            prdc = PRDC(k=_PRDC_K)   # the data against itself: two disjoint random halves (the first pair of sets is released)
-            for lo in range(0, half, batch_size):
-                prdc.feed_real(real_at(perm[lo:min(lo + batch_size, half)]))
-                prdc.feed_fake(real_at(perm[half + lo:min(half + lo + batch_size, 2 * half)]))
-            result.update({name + "_real": value for name, value in prdc.result().items()})
-        for suffix in ("", "_real"):
-            for name in PRDC.KEYS:
-                print(f"PRDC [{name + suffix:>14}] = {result[name + suffix]:.6f} at {cside} x {cside}, k = {_PRDC_K}")
-        print("PRDC: low precision means samples off the data manifold, low recall or coverage means modes missing; compare with "
-              "the _real column (two halves of the data against each other)")
-    if "ndb" in metrics:
-        half = nb_images // 2
-        bins = _ndb_bins(half)
-        need, free = half * 2 * cside * cside * 4, torch.cuda.mem_get_info(device)[0]
-        if need > 0.75 * free:
-            raise ValueError(f"ndb keeps {half} real images of {cside} x {cside} resident: {need} bytes, more than three quarters of "
-                             f"the {free} bytes free on the device")
-        with torch.no_grad():
-            km = KMeans(bins, iterations=_NDB_ITERATIONS, seed=seed)   # the bins: fitted on one random half of the real set
-            for lo in range(0, half, batch_size):
-                km.feed(real_at(perm[lo:min(lo + batch_size, half)]))
-            km.fit()
-            ndb_fake, ndb_real = NDB(km), NDB(km)   # both query sets have `half` images: the z-test's power depends on the size
-            for lo in range(0, half, batch_size):
-                n = min(batch_size, half - lo)
-                ndb_fake.feed(reduced(gen(latents[lo:lo + n].contiguous(), 1.0).contiguous()))
-                ndb_real.feed(real_at(perm[half + lo:half + lo + n]))
-            result.update(ndb_fake.result())
-            result.update({name + "_real": value for name, value in ndb_real.result().items()})
-        last = int(km.changed[-1])
-        print(f"NDB: {bins} k-means bins fitted on {half} real images at {cside} x {cside}; the last of {_NDB_ITERATIONS} iterations "
-              f"changed {last} labels" + ("" if last == 0 else " (not converged: raise the iterations)"))
-        if half < _NDB_PER_BIN * bins:
-            print(f"NDB: fewer than {_NDB_PER_BIN} reference images per bin: the test has little power")
-        for suffix in ("", "_real"):
-            print(f"NDB [{'ndb' + suffix:>8}] = {result['ndb' + suffix]:.6f}, JSD [{'jsd' + suffix:>8}] = {result['jsd' + suffix]:.6f}")
-        print("NDB: ndb well above ndb_real means the samples are spread over the corpus differently from the data: modes missing or "
-              "over-produced; ndb_real is about 0.05 for a held-out half")
+    for name in METRICS_EVERY:
+        if name in metrics:
+            result.update(_RUNNERS[name][0](images, nb_images, perm, seed))
     if output is not None:
         with open(output, "w") as f:
             json.dump(result, f, indent=1)

@@ -348,6 +348,54 @@ def _rows(x: torch.Tensor, what: str) -> torch.Tensor:
     return x.view(x.shape[0], -1)
 
 
+def _check_batch(batch: torch.Tensor, shape: Tuple[int, ...]) -> None:
+    if batch.dim() < 2 or tuple(batch.shape[1:]) != shape or batch.shape[0] < 1:
+        raise ValueError(f"a non-empty batch (B, {', '.join(map(str, shape))}) expected, got {tuple(batch.shape)}")
+
+
+def _blocks(n: int, step: int):
+    """(lo, hi) of the row blocks of at most `step` rows that make up 0 .. n"""
+    for lo in range(0, n, step):
+        yield lo, min(lo + step, n)
+
+
+def _block_rows(block_bytes: int, nr: int, d: int) -> int:
+    """the query rows whose distance block against nr rows of d numbers, with the kernel's workspace, fits block_bytes"""
+    per_row = 8 * nr + nn_ops.nn_tiled_ws_bytes(1, nr, d)
+    return max(1, block_bytes // per_row)
+
+
+def _best_lists(n: int, k: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """the empty (n, k) lists nn_merge fills: float64 distances and int64 ids"""
+    return (torch.full((n, k), nn_ops.EMPTY, dtype=torch.float64, device=device),
+            torch.full((n, k), -1, dtype=torch.int64, device=device))
+
+
+class _RowStore:
+    """The rows `owner` (a class name, for the messages) was fed, kept on the device: every batch is flattened and cloned as it
+    arrives, and the pieces are concatenated once, when the rows are first asked for."""
+
+    def __init__(self, owner: str) -> None:
+        self.owner, self.n, self._parts = owner, 0, []
+
+    def add(self, batch: torch.Tensor, what: str, shape: Optional[Tuple[int, ...]]) -> Tuple[int, ...]:
+        """keep a non-empty float32 cuda batch (B, ...) whose trailing shape is `shape` (None: any); returns that shape"""
+        if batch.dim() < 2 or batch.shape[0] < 1 or batch[0].numel() < 1:
+            raise ValueError(f"{what}: a non-empty batch (B, ...) expected, got {tuple(batch.shape)}")
+        if shape is not None and tuple(batch.shape[1:]) != shape:
+            raise ValueError(f"{what}: a batch (B, {', '.join(map(str, shape))}) expected, got {tuple(batch.shape)}")
+        rows = _rows(batch, f"{self.owner}.{what}")
+        self._parts.append(rows.clone())
+        self.n += rows.shape[0]
+        return tuple(batch.shape[1:])
+
+    def rows(self) -> torch.Tensor:
+        """(n, D) float32"""
+        if len(self._parts) > 1:
+            self._parts = [torch.cat(self._parts)]
+        return self._parts[0]
+
+
 def _sqdist(q: torch.Tensor, qn: torch.Tensor, r: torch.Tensor, out: torch.Tensor) -> None:
     """out (nq, nr) = the distances of every (q[i], r[j]); r goes through in pieces of rows (a pair's value does not depend on
     the piece it is in)"""
@@ -357,9 +405,9 @@ def _sqdist(q: torch.Tensor, qn: torch.Tensor, r: torch.Tensor, out: torch.Tenso
     if step >= nr:
         nn_ops.nn_sqdist(q, r, qn, nn_ops.nn_sqnorm(r), out)
         return
-    for lo in range(0, nr, step):
-        piece = r[lo:lo + step]
-        out[:, lo:lo + step] = nn_ops.nn_sqdist(q, piece, qn, nn_ops.nn_sqnorm(piece))
+    for lo, hi in _blocks(nr, step):
+        piece = r[lo:hi]
+        out[:, lo:hi] = nn_ops.nn_sqdist(q, piece, qn, nn_ops.nn_sqnorm(piece))
 
 
 def pairwise_sqdist(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
@@ -407,13 +455,11 @@ class NearestNeighbours:
                 raise ValueError("query_ids: ids >= 0, or -1 for a query without one, expected")
             self._qid = _ids_to(ids, dev)
         self._qn = nn_ops.nn_sqnorm(self._q)
-        self._best_d = torch.full((nq, k), nn_ops.EMPTY, dtype=torch.float64, device=dev)
-        self._best_i = torch.full((nq, k), -1, dtype=torch.int64, device=dev)
+        self._best_d, self._best_i = _best_lists(nq, k, dev)
         self._fed = 0
 
     def feed(self, batch: torch.Tensor, ids) -> None:
-        if batch.dim() < 2 or tuple(batch.shape[1:]) != self.shape or batch.shape[0] < 1:
-            raise ValueError(f"a non-empty batch (B, {', '.join(map(str, self.shape))}) expected, got {tuple(batch.shape)}")
+        _check_batch(batch, self.shape)
         ids = _id_list(ids, batch.shape[0], "ids")
         if len(set(ids)) != len(ids) or min(ids) < 0:
             raise ValueError("ids: distinct integers >= 0 expected")
@@ -452,40 +498,25 @@ class PRDC:
         if block_bytes < 1:
             raise ValueError(f"block_bytes must be positive, got {block_bytes}")
         self.k, self.block_bytes, self.shape = k, int(block_bytes), None
-        self._fed = {"real": [], "fake": []}
-        self._n = {"real": 0, "fake": 0}
+        self._real, self._fake = _RowStore("PRDC"), _RowStore("PRDC")   # the two sets share the one trailing shape
         self._per_sample = None
 
-    def _feed(self, which: str, batch: torch.Tensor) -> None:
-        if batch.dim() < 2 or batch.shape[0] < 1 or batch[0].numel() < 1:
-            raise ValueError(f"feed_{which}: a non-empty batch (B, ...) expected, got {tuple(batch.shape)}")
-        if self.shape is not None and tuple(batch.shape[1:]) != self.shape:
-            raise ValueError(f"feed_{which}: a batch (B, {', '.join(map(str, self.shape))}) expected, got {tuple(batch.shape)}")
-        rows = _rows(batch, f"PRDC.feed_{which}")
-        self.shape = tuple(batch.shape[1:])
-        self._fed[which].append(rows.clone())
-        self._n[which] += rows.shape[0]
+    def _feed(self, store: _RowStore, what: str, batch: torch.Tensor) -> None:
+        self.shape = store.add(batch, what, self.shape)
         self._per_sample = None
 
     def feed_real(self, batch: torch.Tensor) -> None:
-        self._feed("real", batch)
+        self._feed(self._real, "feed_real", batch)
 
     def feed_fake(self, batch: torch.Tensor) -> None:
-        self._feed("fake", batch)
-
-    def _block_rows(self, nr: int, d: int) -> int:
-        per_row = 8 * nr + nn_ops.nn_tiled_ws_bytes(1, nr, d)
-        return max(1, self.block_bytes // per_row)
+        self._feed(self._fake, "feed_fake", batch)
 
     def _radius(self, x: torch.Tensor, xn: torch.Tensor) -> torch.Tensor:
         """every row's distance to its k-th nearest other row of x"""
         n, d, dev = x.shape[0], x.shape[1], x.device
         ids = torch.arange(n, dtype=torch.int64, device=dev)
-        best_d = torch.full((n, self.k), nn_ops.EMPTY, dtype=torch.float64, device=dev)
-        best_i = torch.full((n, self.k), -1, dtype=torch.int64, device=dev)
-        step = self._block_rows(n, d)
-        for lo in range(0, n, step):
-            hi = min(lo + step, n)
+        best_d, best_i = _best_lists(n, self.k, dev)
+        for lo, hi in _blocks(n, _block_rows(self.block_bytes, n, d)):
             dist = nn_ops.nn_sqdist_tiled(x[lo:hi], x, xn[lo:hi], xn)
             nn_ops.nn_merge(dist, ids, best_d[lo:hi], best_i[lo:hi], ids[lo:hi])
         return best_d[:, self.k - 1].contiguous()
@@ -495,9 +526,7 @@ class PRDC:
         nq, nr, d, dev = q.shape[0], r.shape[0], q.shape[1], q.device
         count = torch.zeros(nq, dtype=torch.int64, device=dev)
         rowmin = torch.full((nq,), float("inf"), dtype=torch.float64, device=dev)
-        step = self._block_rows(nr, d)
-        for lo in range(0, nq, step):
-            hi = min(lo + step, nq)
+        for lo, hi in _blocks(nq, _block_rows(self.block_bytes, nr, d)):
             dist = nn_ops.nn_sqdist_tiled(q[lo:hi], r, qn[lo:hi], rn)
             nn_ops.prdc_scan(dist, radius, count[lo:hi], rowmin[lo:hi])
         return count, rowmin
@@ -506,12 +535,11 @@ class PRDC:
         """device tensors: radius_real / radius_fake (float64, the k-th nearest other member of the own set), count_fake (int64,
         per fake: the real balls it lies in), count_real (int64, per real: the fake balls it lies in), nearest_fake (float64, per
         real: the distance to the nearest fake)"""
-        if min(self._n.values()) < self.k + 1:
-            raise ValueError(f"{self._n['real']} real and {self._n['fake']} fake images fed, at least k + 1 = {self.k + 1} of each "
+        if min(self._real.n, self._fake.n) < self.k + 1:
+            raise ValueError(f"{self._real.n} real and {self._fake.n} fake images fed, at least k + 1 = {self.k + 1} of each "
                              "expected")
         if self._per_sample is None:
-            real, fake = (torch.cat(self._fed[w]) if len(self._fed[w]) > 1 else self._fed[w][0] for w in ("real", "fake"))
-            self._fed = {"real": [real], "fake": [fake]}
+            real, fake = self._real.rows(), self._fake.rows()
             rn, fn = nn_ops.nn_sqnorm(real), nn_ops.nn_sqnorm(fake)
             radius_real, radius_fake = self._radius(real, rn), self._radius(fake, fn)
             count_fake, _ = self._scan(fake, fn, real, rn, radius_real)
@@ -522,7 +550,7 @@ class PRDC:
 
     def result(self) -> Dict[str, float]:
         p = self.per_sample()
-        n_real, n_fake = self._n["real"], self._n["fake"]
+        n_real, n_fake = self._real.n, self._fake.n
         # four integer sums on the device, one copy, the divisions on the host: exact counts over exact divisors
         inside, seen, balls, covered = torch.stack([(p["count_fake"] > 0).sum(), (p["count_real"] > 0).sum(), p["count_fake"].sum(),
                                                     (p["nearest_fake"] <= p["radius_real"]).sum()]).tolist()
@@ -589,33 +617,21 @@ class KMeans:
                 raise ValueError(f"init_ids: {bins} distinct positions >= 0 expected")
         self.bins, self.iterations, self.seed, self.init_ids, self.block_bytes = bins, iterations, seed, init_ids, block_bytes
         self.shape = None
-        self._fed, self._n, self._out = [], 0, None
+        self._fed, self._out = _RowStore("KMeans"), None
 
     def feed(self, batch: torch.Tensor) -> None:
-        if batch.dim() < 2 or batch.shape[0] < 1 or batch[0].numel() < 1:
-            raise ValueError(f"feed: a non-empty batch (B, ...) expected, got {tuple(batch.shape)}")
-        if self.shape is not None and tuple(batch.shape[1:]) != self.shape:
-            raise ValueError(f"feed: a batch (B, {', '.join(map(str, self.shape))}) expected, got {tuple(batch.shape)}")
-        rows = _rows(batch, "KMeans.feed")
-        self.shape = tuple(batch.shape[1:])
-        self._fed.append(rows.clone())
-        self._n += rows.shape[0]
+        self.shape = self._fed.add(batch, "feed", self.shape)
         self._out = None
-
-    def _block_rows(self, d: int) -> int:
-        per_row = 8 * self.bins + nn_ops.nn_tiled_ws_bytes(1, self.bins, d)
-        return max(1, self.block_bytes // per_row)
 
     def _assign(self, x: torch.Tensor, xn: torch.Tensor, c: torch.Tensor, labels: torch.Tensor, mind: torch.Tensor,
                 changed: torch.Tensor) -> None:
         """labels, mind and the one-element changed of every row of x against the centroids c"""
-        n, cn, step = x.shape[0], nn_ops.nn_sqnorm(c), self._block_rows(x.shape[1])
+        n, cn, step = x.shape[0], nn_ops.nn_sqnorm(c), _block_rows(self.block_bytes, self.bins, x.shape[1])
         if step >= n:
             km_ops.km_assign(nn_ops.nn_sqdist_tiled(x, c, xn, cn), labels, mind, changed)
             return
         part = torch.empty((n + step - 1) // step, dtype=torch.int64, device=x.device)
-        for b, lo in enumerate(range(0, n, step)):
-            hi = min(lo + step, n)
+        for b, (lo, hi) in enumerate(_blocks(n, step)):
             km_ops.km_assign(nn_ops.nn_sqdist_tiled(x[lo:hi], c, xn[lo:hi], cn), labels[lo:hi], mind[lo:hi], part[b:b + 1])
         changed.copy_(part.sum().reshape(1))
 
@@ -623,7 +639,7 @@ class KMeans:
         """everything from the initial centroids to the final assignment, as launches on the current stream; the host does not wait"""
         if self._out is not None:
             return self
-        n, k = self._n, self.bins
+        n, k = self._fed.n, self.bins
         if n < k:
             raise ValueError(f"{n} images fed, at least as many as the {k} bins expected")
         if n > km_ops.MAX_N:
@@ -632,8 +648,7 @@ class KMeans:
             torch.randperm(n, generator=torch.Generator().manual_seed(self.seed))[:k].tolist()
         if max(ids) >= n:
             raise ValueError(f"init_ids: positions below the {n} images fed expected, got {max(ids)}")
-        x = torch.cat(self._fed) if len(self._fed) > 1 else self._fed[0]
-        self._fed = [x]
+        x = self._fed.rows()
         dev = x.device
         xn = nn_ops.nn_sqnorm(x)
         c = x.index_select(0, _ids_to(ids, dev)).contiguous()
@@ -653,7 +668,7 @@ class KMeans:
 
     def _fitted(self, name: str) -> torch.Tensor:
         if self._out is None:
-            if not self._n:
+            if not self._fed.n:
                 raise ValueError("no image fed yet")
             self.fit()
         return self._out[name]
@@ -683,8 +698,7 @@ class KMeans:
         bin) and the squared distance to its centroid"""
         if self.shape is None:
             raise ValueError("no image fed yet")
-        if batch.dim() < 2 or tuple(batch.shape[1:]) != self.shape or batch.shape[0] < 1:
-            raise ValueError(f"a non-empty batch (B, {', '.join(map(str, self.shape))}) expected, got {tuple(batch.shape)}")
+        _check_batch(batch, self.shape)
         rows = _rows(batch, "KMeans.assign")
         c, dev = self.centroids, rows.device
         labels = torch.full((rows.shape[0],), -1, dtype=torch.int32, device=dev)

@@ -109,6 +109,37 @@ def test_host_query_and_argument_checks_need_no_gpu():
     assert metrics.PRDC.KEYS == P.KEYS
 
 
+def test_the_row_store_refuses_in_the_words_of_the_class_that_feeds_it():
+    """PRDC (two stores, one trailing shape between them) and KMeans (one) keep what they are fed in metrics._RowStore: an empty
+    batch, another trailing shape and a CPU tensor are refused with the text each class has always given, and nothing is kept"""
+    from musicgan_amd import _lib, metrics
+    z = torch.zeros
+    prdc, km = metrics.PRDC(k=3), metrics.KMeans(bins=2)
+    feeds = (("PRDC", "feed_real", prdc.feed_real, prdc), ("PRDC", "feed_fake", prdc.feed_fake, prdc), ("KMeans", "feed", km.feed, km))
+    for owner, what, feed, obj in feeds:
+        store = metrics._RowStore(owner)
+        for add in (feed, lambda batch: store.add(batch, what, obj.shape)):
+            for empty in (z(0, 2, 8, 8), z(4), z(4, 0, 8)):
+                with pytest.raises(ValueError) as err:
+                    add(empty)
+                assert str(err.value) == f"{what}: a non-empty batch (B, ...) expected, got {tuple(empty.shape)}"
+            with pytest.raises(_lib.MusicGanHipError) as err:
+                add(z(4, 2, 8, 8))                                         # all in order, but not on a GPU
+            assert str(err.value) == f"{owner}.{what}: tensors on a ROCm GPU expected (no CPU fallback)"
+        assert obj.shape is None                                           # a refused batch does not set the shape
+        obj.shape = (2, 8, 8)                                              # as after a first batch of 2 x 8 x 8 images
+        for add in (feed, lambda batch: store.add(batch, what, obj.shape)):
+            for other in (z(4, 2, 8, 4), z(4, 128)):
+                with pytest.raises(ValueError) as err:
+                    add(other)
+                assert str(err.value) == f"{what}: a batch (B, 2, 8, 8) expected, got {tuple(other.shape)}"
+        obj.shape = None
+        assert store.n == 0 and not store._parts
+    assert prdc._real.n == prdc._fake.n == km._fed.n == 0
+    with pytest.raises(ValueError, match="0 real and 0 fake images fed"):
+        prdc.result()
+
+
 def test_prdc_kernels_do_not_use_scratch_memory():
     from musicgan_amd import _build
     _build.build()

@@ -11,6 +11,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import nn_ref as R  # noqa: E402
+from eval_corpus import tiny_corpus  # noqa: E402
 import poison  # noqa: E402
 import prdc_ref as P  # noqa: E402
 
@@ -227,20 +228,11 @@ def test_evaluate_with_prdc_on_a_tiny_corpus(tmp_path, capsys, monkeypatch):
     import musicgan_amd
     from musicgan_amd import audio, ops
     from musicgan_amd.__main__ import main
-    from musicgan_amd.audio import wavio
     from musicgan_amd.networks import Generator
-    rng = torch.Generator().manual_seed(6)
-    wav_dir, data_dir = tmp_path / "wav", tmp_path / "data"
-    wav_dir.mkdir()
-    for i in range(4):
-        wavio.save(str(wav_dir / f"s{i}.wav"), torch.rand(2, 256 * 1030, generator=rng) - 0.5, 44100)
-    musicgan_amd.create_dataset(str(wav_dir / "*.wav"), str(data_dir))   # 4 files x 2 samples
+    data_dir, ck = tiny_corpus(tmp_path, files=4, seed=6, level=2)      # 4 files x 2 samples
     dataset = audio.PackedAudioDataset(str(data_dir)) if audio.has_packed(str(data_dir)) else audio.AudioDataset(str(data_dir))
     n = len(dataset)
     assert n == 8
-    torch.manual_seed(0)
-    ck = str(tmp_path / "gen2.pt")
-    torch.save(Generator(8, end_layer=2).state_dict(), ck)
     capsys.readouterr()
     kw = dict(level=2, nb_images=n, batch_size=3, seed=1)
     before = musicgan_amd.evaluate(ck, 8, str(data_dir), metrics=("swd", "msssim", "nn"), **kw)

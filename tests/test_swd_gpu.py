@@ -10,6 +10,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import swd_ref as R  # noqa: E402
+from eval_corpus import tiny_corpus  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -221,17 +222,7 @@ def test_feeding_does_not_synchronise():
 def test_evaluate_on_a_tiny_corpus(tmp_path, capsys):
     import musicgan_amd
     from musicgan_amd.__main__ import main
-    from musicgan_amd.audio import wavio
-    from musicgan_amd.networks import Generator
-    rng = torch.Generator().manual_seed(5)
-    wav_dir, data_dir = tmp_path / "wav", tmp_path / "data"
-    wav_dir.mkdir()
-    for i in range(2):
-        wavio.save(str(wav_dir / f"s{i}.wav"), torch.rand(2, 256 * 1030, generator=rng) - 0.5, 44100)
-    musicgan_amd.create_dataset(str(wav_dir / "*.wav"), str(data_dir))   # 2 files x 2 samples
-    torch.manual_seed(0)
-    ck = str(tmp_path / "gen2.pt")
-    torch.save(Generator(8, end_layer=2).state_dict(), ck)
+    data_dir, ck = tiny_corpus(tmp_path, files=2, seed=5, level=2)      # 2 files x 2 samples
     capsys.readouterr()
     first = musicgan_amd.evaluate(ck, 8, str(data_dir), level=2, nb_images=8, batch_size=3, seed=1)
     text = capsys.readouterr().out
