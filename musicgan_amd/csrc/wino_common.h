@@ -53,4 +53,30 @@ __device__ __forceinline__ f32x4 pk_sub4(f32x4 x, f32x4 y) {
   return f32x4{lo[0], lo[1], hi[0], hi[1]};
 }
 
+// The filter image of a workgroup in LDS -- [chunk][PER 16-byte pieces], a verbatim copy of `nchunk` runs of the packed bank (run ch =
+// pieces src_first + ch * src_stride .. + PER - 1) -- filled by LDS-DMA (`buffer_load_dwordx4 ... lds`, wino_wgrad_rows.hip): one wave
+// instruction copies 64 consecutive pieces = 1 KiB, needs no staging registers, and EVERY instruction of the fill is requested before
+// anybody waits (the copy through registers it replaces compiled to load / s_waitcnt vmcnt(0) / ds_write per 16 bytes and thread:
+// 12-27 dependent memory round trips in front of every launch's first MFMA).  Wave `wave` of NWAVE issues instructions wave, wave +
+// NWAVE, ... of nchunk * ceil(PER / 64); an instruction never crosses a chunk boundary, and the last one of a chunk whose PER is no
+// multiple of 64 runs with the lanes behind the chunk switched off (an out-of-range lane would write zeros, tools/hwtests/
+// lds_dma_oob.hip -- onto the next chunk's image or behind the allocation).  The descriptor ends with the packed bank.
+// Asynchronous: wino_bank_landed() (this wave's pieces), then the workgroup barrier, before the first read.
+typedef __attribute__((address_space(3))) void* wino_lds_ptr;
+template <int PER, int NWAVE>
+__device__ __forceinline__ void wino_bank_fill(float* lds, const float* bank, int bank_bytes, int nchunk, int src_stride, int src_first,
+                                               int wave, int lane) {
+  constexpr int IPC = (PER + 63) / 64;  // instructions per chunk
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bank), 0, bank_bytes, 0x00020000);
+  const int n = nchunk * IPC;
+  for (int q = wave; q < n; q += NWAVE) {  // (wave-uniform)
+    const int ch = q / IPC, j = q - ch * IPC;
+    float* dst = lds + (ch * PER + 64 * j) * 4;
+    const int so = (src_first + ch * src_stride + 64 * j) * 16;
+    if ((PER % 64) == 0 || 64 * j + lane < PER) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (wino_lds_ptr)dst, 16, lane * 16, so, 0, 0);
+  }
+}
+// (a "memory" clobber: the kernels' LDS reads are inline assembly and must not move above the wait)
+__device__ __forceinline__ void wino_bank_landed() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+
 }  // namespace

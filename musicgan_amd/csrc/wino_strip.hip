@@ -80,7 +80,6 @@ __device__ __forceinline__ void sk_tie(f32x4& v) { asm volatile("" : "+v"(v)); }
 template <int NIW, int NLDS, int NWAVE, int KIND, bool POOL>
 __device__ __forceinline__ void strip_body(const WinoArgs& a, const int ct0, const int wg, const int G) {
   constexpr int kind = KIND;
-  constexpr int NTHR = 64 * NWAVE;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* Us = smem;  // [chunk][NIW tiles][8 component pairs][64 lanes][4]: a verbatim copy of the packed global layout
   const int tid = threadIdx.x;
@@ -90,16 +89,14 @@ __device__ __forceinline__ void strip_body(const WinoArgs& a, const int ct0, con
   const int Ht = a.H >> 1, Wt = a.W >> 1;
   const int PP = Ht * Wt;  // one pooled plane
 
-  {  // the filter bank of this workgroup's out-channels, once
-    const int n4 = a.nchunk * NLDS * 512;  // 16-byte pieces
-    const f32x4* src = reinterpret_cast<const f32x4*>(a.up);
-    f32x4* dst = reinterpret_cast<f32x4*>(Us);
-    for (int i = tid; i < n4; i += NTHR) {
-      const int ch = i / (NLDS * 512), r = i - ch * (NLDS * 512);
-      dst[i] = src[((size_t)ch * a.NT + ct0) * 512 + r];
-    }
-  }
-  __syncthreads();
+  const int groups_y = Ht / NWAVE;
+  const int nitems = a.N * groups_y * a.blocks_x;
+  const int first = mg_xcd_remap(wg, G);  // (row sizes are multiples of 8: workgroup wg of a row sits on XCD wg % 8)
+  if (first >= nitems) return;            // (the whole workgroup, in front of the fill and its barrier)
+  // The filter bank of this workgroup's out-channels, once: per chunk NLDS * 512 consecutive 16-byte pieces of the packed bank, every
+  // one of them requested here; the first block's rows are requested right behind them and transformed before the barrier in front of
+  // the first MFMAs -- the launch pays one memory round trip instead of one per 8 KB of filters and then another for its rows.
+  wino_bank_fill<NLDS * 512, NWAVE>(Us, a.up, a.nchunk * a.NT * 8192, a.nchunk, a.NT * 512, ct0 * 512, wave, lane);
 
   // Addressing: every global access is  base(image) + [lane part: VGPR, fixed for the kernel] + [block / row / plane part: SGPR].
   // Work items: groups of NWAVE vertically adjacent tile blocks (16 tiles x 1 tile row), group g = (image * groups_y + gy) *
@@ -108,10 +105,6 @@ __device__ __forceinline__ void strip_body(const WinoArgs& a, const int ct0, con
   // rows a block shares with the block below are read by two waves of one workgroup at about the same time.  (Measured instead: a
   // wave walking a vertical segment top to bottom, re-reading the shared rows one block time later -- by then they have left the
   // 4 MB L2 of the XCD: rocprofv3 FETCH_SIZE 2.5x the input instead of 1.7x, 32 -> 16 @512 x 18 images, and 15 % slower.)
-  const int groups_y = Ht / NWAVE;
-  const int nitems = a.N * groups_y * a.blocks_x;
-  const int first = mg_xcd_remap(wg, G);  // (row sizes are multiples of 8: workgroup wg of a row sits on XCD wg % 8)
-  if (first >= nitems) return;
   const int dbx = G % a.blocks_x, dgy = (G / a.blocks_x) % groups_y, dn = G / (a.blocks_x * groups_y);
   int bx = first % a.blocks_x, gy = (first / a.blocks_x) % groups_y, n0 = first / (a.blocks_x * groups_y);
   int item = first;
@@ -329,7 +322,9 @@ __device__ __forceinline__ void strip_body(const WinoArgs& a, const int ct0, con
   const int nch = a.nchunk;
   block_geometry();
   load_rows(0);
+  wino_bank_landed();  // (the bank's pieces and the rows share one in-order counter: the transform below needs the rows, the last requests)
   transform_rows();
+  __syncthreads();     // every wave's pieces of the bank are in LDS
 #pragma nounroll
   for (;;) {
     const int ebx = bx, eby = by, en0 = n0;  // this block, for the epilogue

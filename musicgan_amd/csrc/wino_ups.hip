@@ -25,6 +25,7 @@
 
 #include "mg_common.h"
 #include "pack_kernels.h"
+#include "wino_common.h"
 
 namespace {
 
@@ -136,22 +137,12 @@ struct WuWalk {
   }
 };
 
-// the same for a launch that owns NT of nt_total tiles: per chunk a run of NT x 9 x 128 floats out of nt_total x 9 x 128
-__device__ __forceinline__ void wu_load_bank_tiles(float* Us, const float* up, int nchunk, int nt, int nt_total, int tile0, int tid) {
-  const int per = nt * 9 * 32;  // 16-byte pieces per chunk
-  f32x4* dst = reinterpret_cast<f32x4*>(Us);
-  for (int i = tid; i < nchunk * per; i += 64 * WU_NWAVE) {
-    const int ch = i / per, r = i - ch * per;
-    dst[i] = reinterpret_cast<const f32x4*>(up)[(size_t)(ch * nt_total + tile0) * 9 * 32 + r];
-  }
-  __syncthreads();
-}
-
-__device__ __forceinline__ void wu_load_bank(float* Us, const float* up, int n16, int tid) {
-  const f32x4* src = reinterpret_cast<const f32x4*>(up);
-  f32x4* dst = reinterpret_cast<f32x4*>(Us);
-  for (int i = tid; i < n16; i += 64 * WU_NWAVE) dst[i] = src[i];
-  __syncthreads();
+// The filter bank of a launch -> LDS: per chunk the run of NT x 9 x 32 16-byte pieces of its tiles (tile0 .. tile0 + NT - 1 of nt_total;
+// all of them unless the data gradient runs as two tile groups), by LDS-DMA with every piece requested at once (wino_bank_fill,
+// wino_common.h).  A chunk of an odd tile count ends in half an instruction (288 NT pieces, 64 per instruction): lanes switched off.
+template <int NT>
+__device__ __forceinline__ void wu_fill_bank(float* Us, const WuArgs& a, int wave, int lane) {
+  wino_bank_fill<NT * 9 * 32, WU_NWAVE>(Us, a.up, a.nchunk * a.nt_total * (9 * 512), a.nchunk, a.nt_total * 9 * 32, a.tile0 * 9 * 32, wave, lane);
 }
 
 // ------------------------------------------------------------------------------------------------ forward
@@ -161,11 +152,11 @@ __global__ void __launch_bounds__(64 * WU_NWAVE, 1) winoups_fwd(const WuArgs a) 
   const int tid = threadIdx.x, lane = tid & 63, col = lane & 15, rq = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int HWl = a.Hl * a.Wl, H = 2 * a.Hl, W = 2 * a.Wl, HW = H * W;
-  wu_load_bank(Us, a.up, a.nchunk * NT * 9 * 32, tid);
-  const unsigned us_addr = (unsigned)reinterpret_cast<size_t>(Us + lane * 2);  // (low 32 bits of a shared-aperture address = LDS offset)
   WuWalk w;
   w.init(blockIdx.x, a.G, a.N, a.Hl / WU_NWAVE, a.blocks_x);
-  if (w.item >= w.nitems) return;
+  if (w.item >= w.nitems) return;  // (the whole workgroup, in front of the fill and its barrier)
+  wu_fill_bank<NT>(Us, a, wave, lane);
+  const unsigned us_addr = (unsigned)reinterpret_cast<size_t>(Us + lane * 2);  // (low 32 bits of a shared-aperture address = LDS offset)
 
   // input: lane part = channel 2 rq of the chunk, own low-res pixel; scalar part = image, chunk, k-step, row, block
   const int lp = ((2 * rq) * HWl + col) * 4;
@@ -240,7 +231,9 @@ __global__ void __launch_bounds__(64 * WU_NWAVE, 1) winoups_fwd(const WuArgs a) 
   }
   int ty = w.gy * WU_NWAVE + wave;
   geometry(ty);
-  load_rows(0);
+  load_rows(0);  // (requested behind the bank's pieces: one memory round trip for both)
+  wino_bank_landed();
+  __syncthreads();  // every wave's pieces of the bank are in LDS
 #pragma nounroll
   for (;;) {
     const int ebx = w.bx, ety = ty, en = w.n;
@@ -360,12 +353,11 @@ __global__ void __launch_bounds__(64 * WU_NWAVE, 1) winoups_dgrad(const WuArgs a
   const int tid = threadIdx.x, lane = tid & 63, col = lane & 15, rq = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int HWl = a.Hl * a.Wl, H = 2 * a.Hl, W = 2 * a.Wl, HW = H * W;
-  if (a.nt_total == NT) wu_load_bank(Us, a.up, a.nchunk * NT * 9 * 32, tid);
-  else wu_load_bank_tiles(Us, a.up, a.nchunk, NT, a.nt_total, a.tile0, tid);
-  const unsigned us_addr = (unsigned)reinterpret_cast<size_t>(Us + lane * 2);  // (low 32 bits of a shared-aperture address = LDS offset)
   WuWalk w;
   w.init(blockIdx.x, a.G, a.N, a.Hl / WU_NWAVE, a.blocks_x);
-  if (w.item >= w.nitems) return;
+  if (w.item >= w.nitems) return;  // (the whole workgroup, in front of the fill and its barrier)
+  wu_fill_bank<NT>(Us, a, wave, lane);
+  const unsigned us_addr = (unsigned)reinterpret_cast<size_t>(Us + lane * 2);  // (low 32 bits of a shared-aperture address = LDS offset)
 
   const int lp = ((2 * rq) * HW + 2 * col) * 4;
   f32x2 rP[2][4];  // [k-step][patch row]: own pixel pair
@@ -421,7 +413,9 @@ __global__ void __launch_bounds__(64 * WU_NWAVE, 1) winoups_dgrad(const WuArgs a
   f32x4 acc[9][NT];
   int ty = w.gy * WU_NWAVE + wave;
   geometry(ty);
-  load_rows(0);
+  load_rows(0);  // (requested behind the bank's pieces: one memory round trip for both)
+  wino_bank_landed();
+  __syncthreads();  // every wave's pieces of the bank are in LDS
 #pragma nounroll
   for (;;) {
     const int ebx = w.bx, ety = ty, en = w.n;
