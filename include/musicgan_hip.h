@@ -606,6 +606,15 @@ int mg_griffin_lim(const float* magn, float* z_c64, float* wav_out, double* conv
 int64_t mg_phase_vocoder_len(int64_t frames, int p, int q);
 size_t mg_phase_vocoder_ws_bytes(int64_t frames, int p, int q);
 int mg_phase_vocoder(const float* x_c64, float* out_c64, void* ws, size_t ws_bytes, int64_t frames, int p, int q, mg_stream_t stream);
+/* The same with identity phase locking (Laroche & Dolson 1999; definition: DESIGN.md, "Phase locking"): every bin follows the
+ * nearest peak of its output frame's magnitude and keeps against it the phase difference of the analysis frame.
+ * mg_phase_vocoder_locked_ws_bytes: host only; 8 bytes per input bin, 18 per output bin (the peak each bin follows, int16; its phase
+ *   step and its magnitude, float64) and 20 per row and tile of 256 output frames; 0 where mg_phase_vocoder_ws_bytes gives 0.
+ * mg_phase_vocoder_locked: arguments, checks and error codes of mg_phase_vocoder.  Five launches on `stream` (four up to 256 output
+ *   frames), no allocation, no synchronisation, no atomics, one order for every sum: the same bits on every run. */
+size_t mg_phase_vocoder_locked_ws_bytes(int64_t frames, int p, int q);
+int mg_phase_vocoder_locked(const float* x_c64, float* out_c64, void* ws, size_t ws_bytes, int64_t frames, int p, int q,
+                            mg_stream_t stream);
 
 /* ------------------------------------------------------------------ loudness and true peak (csrc/loudness.hip)
  * Programme loudness after ITU-R BS.1770-4 / EBU R128 of a waveform x: C <= 8 rows of L float32 samples, `row_stride` floats apart

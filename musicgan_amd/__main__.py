@@ -59,6 +59,9 @@ _MODES = {
         (("--preserve-transients",), dict(dest="preserve_transients", action="store_true",
                                           help="with --stretch / --pitch: re-time only the harmonic part of every variant with the "
                                                "phase vocoder and overlap-add its percussive part, so that drum hits stay sharp")),
+        (("--phase-lock",), dict(dest="phase_lock", action="store_true",
+                                 help="with --stretch / --pitch: identity phase locking in the phase vocoder, so that the bins of "
+                                      "one partial keep their phase differences and moving pitches do not warble")),
         (("--component",), dict(choices=("harmonic", "percussive"), default=None,
                                 help="code only this component of every spectrum (median-filtering harmonic / percussive "
                                      "separation), the original's and each variant's")),
@@ -66,6 +69,7 @@ _MODES = {
         lambda a: {**({"resample": True} if a.resample else {}), **({"stretch": a.stretch} if a.stretch else {}),
                    **({"pitch": a.pitch} if a.pitch else {}),
                    **({"preserve_transients": True} if a.preserve_transients else {}),
+                   **({"phase_lock": True} if a.phase_lock else {}),
                    **({"component": a.component} if a.component is not None else {})}),
     "train": ("train", "train", [
         (("run",), dict(type=str, metavar="RUN_NAME")),

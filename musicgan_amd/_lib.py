@@ -199,6 +199,8 @@ SIGNATURES = {
     "mg_phase_vocoder_len": (c_int64, [c_int64, c_int, c_int]),
     "mg_phase_vocoder_ws_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "mg_phase_vocoder": (c_int, [_P, _P, _P, c_size_t, c_int64, c_int, c_int, _P]),
+    "mg_phase_vocoder_locked_ws_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "mg_phase_vocoder_locked": (c_int, [_P, _P, _P, c_size_t, c_int64, c_int, c_int, _P]),
     "mg_loudness_chunk": (c_int, []),
     "mg_loudness_ws_bytes": (c_size_t, [c_int, c_int64, c_int]),
     "mg_loudness_energy": (c_int, [_P, c_int, c_int64, c_int64, c_int, POINTER(ctypes.c_double), _P, _P, c_size_t, _P]),

@@ -156,18 +156,29 @@ def istft(complex_values: th.Tensor) -> th.Tensor:
     return gl_ops.istft_1024(complex_values.to(dev, th.complex64).contiguous())
 
 
-def phase_vocoder(complex_specgrams: th.Tensor, rate) -> th.Tensor:
+def _check_phase_lock(phase_lock) -> None:
+    if not isinstance(phase_lock, bool):
+        raise ValueError(f"phase_lock must be True or False, got {phase_lock!r}")
+
+
+def phase_vocoder(complex_specgrams: th.Tensor, rate, phase_lock: bool = False) -> th.Tensor:
     """torchaudio.functional.phase_vocoder for this package's STFT (1024 / 256, phase_advance pi k / 2): complex (512, T), T >= 1 ->
     complex64 (512, ceil(T / rate)) on the device; a CPU tensor is moved there first.  rate (above 1: faster and shorter) is an int,
     a fractions.Fraction or a float in [1/8, 8]; a float is turned into Fraction(rate).limit_denominator(1000), so that the time axis
-    is integer arithmetic.  Magnitudes and angles are float32, the phase is accumulated in float64 modulo 2 pi."""
+    is integer arithmetic.  Magnitudes and angles are float32, the phase is accumulated in float64 modulo 2 pi.
+    phase_lock: identity phase locking (Laroche & Dolson 1999): the bins around every magnitude peak of an output frame keep the
+    phase differences they have in the analysis frame, which takes the amplitude warble out of moving pitches."""
     r = pv_ops.as_rate(rate)
+    _check_phase_lock(phase_lock)
     if complex_specgrams.dim() != 2 or complex_specgrams.shape[0] != constant.N_FFT // 2 or complex_specgrams.shape[1] < 1:
         raise ValueError(f"a ({constant.N_FFT // 2}, T >= 1) spectrum expected, got {tuple(complex_specgrams.shape)}")
     if not complex_specgrams.is_complex():
         raise ValueError(f"a complex spectrum expected, got {complex_specgrams.dtype}")
     dev = complex_specgrams.device if complex_specgrams.is_cuda else _device()
-    return pv_ops.phase_vocoder(complex_specgrams.to(dev, th.complex64).contiguous(), r.numerator, r.denominator)
+    x = complex_specgrams.to(dev, th.complex64).contiguous()
+    if not phase_lock:
+        return pv_ops.phase_vocoder(x, r.numerator, r.denominator)
+    return pv_ops.phase_vocoder(x, r.numerator, r.denominator, lock=True)
 
 
 def hpss(complex_spec: th.Tensor, kernel_size=31, power: float = 2.0, margin=1.0, mask: bool = False) -> Tuple[th.Tensor, th.Tensor]:
@@ -205,31 +216,34 @@ def percussive(waveform: th.Tensor, kernel_size=31, power: float = 2.0, margin=1
     return _component(waveform, 1, kernel_size, power, margin)
 
 
-def time_stretch(waveform: th.Tensor, rate, preserve_transients: bool = False) -> th.Tensor:
+def time_stretch(waveform: th.Tensor, rate, preserve_transients: bool = False, phase_lock: bool = False) -> th.Tensor:
     """mono (samples,) float waveform -> the same sound `rate` times as fast at the same pitch: `istft(phase_vocoder(
     stft_from_waveform(waveform), rate))`, 256 * (n - 1) samples for n = ceil((1 + samples // 256) / rate) frames; n < 4 raises
     the ValueError of `istft`.  rate: as `phase_vocoder` takes it.
     preserve_transients (Driedger, Mueller, Ewert 2014): the spectrum is split by `hpss`; only the harmonic part goes through the
     phase vocoder, the percussive part is re-timed by overlap-add of short frames, which copies every hit as it is:
     `istft(phase_vocoder(Xh, rate)) + ola_stretch(istft(Xp), p, q, 256 * (n - 1))`, the same length; fewer than 4 frames on either
-    side raise the ValueError of `istft`."""
+    side raise the ValueError of `istft`.  phase_lock: passed to `phase_vocoder`."""
     r = pv_ops.as_rate(rate)
+    _check_phase_lock(phase_lock)
     if waveform.dim() != 1 or not waveform.is_floating_point():
         raise ValueError(f"a mono floating-point waveform (samples,) expected, got {tuple(waveform.shape)} {waveform.dtype}")
     if not preserve_transients:
-        return istft(phase_vocoder(stft_from_waveform(waveform), r))
-    return retime_preserving_transients(stft_from_waveform(waveform), r, as_waveform=True)
+        return istft(phase_vocoder(stft_from_waveform(waveform), r, phase_lock=phase_lock))
+    return retime_preserving_transients(stft_from_waveform(waveform), r, as_waveform=True, phase_lock=phase_lock)
 
 
-def retime_preserving_transients(complex_spec: th.Tensor, rate, as_waveform: bool = False) -> th.Tensor:
+def retime_preserving_transients(complex_spec: th.Tensor, rate, as_waveform: bool = False, phase_lock: bool = False) -> th.Tensor:
     """complex64 (512, T >= 4) on the device -> the spectrum (512, n = ceil(T / rate)) of the transient-preserving re-timing:
     `phase_vocoder(Xh, rate) + stft(ola_stretch(istft(Xp), p, q, 256 * (n - 1)))` for (Xh, Xp) = hpss(X); as_waveform: the
-    waveform `istft(phase_vocoder(Xh, rate)) + ola_stretch(...)` of 256 * (n - 1) samples instead (what `time_stretch` returns)."""
+    waveform `istft(phase_vocoder(Xh, rate)) + ola_stretch(...)` of 256 * (n - 1) samples instead (what `time_stretch` returns).
+    phase_lock: the harmonic part goes through the phase-locked vocoder (the configuration of Driedger et al.)."""
     r = pv_ops.as_rate(rate)
+    _check_phase_lock(phase_lock)
     xh, xp = hpss(complex_spec)
     samples = hpss_ops.stretched_samples(complex_spec.shape[1], r)
     hits = hpss_ops.ola_stretch(istft(xp), r.numerator, r.denominator, samples)
-    tones = phase_vocoder(xh, r)
+    tones = phase_vocoder(xh, r, phase_lock=phase_lock)
     if as_waveform:
         return istft(tones) + hits
     return tones + ops.stft_1024(hits)
@@ -243,13 +257,14 @@ def pitch_ratio(n_steps) -> Fraction:
     return Fraction(2 ** (float(n_steps) / 12)).limit_denominator(64)
 
 
-def pitch_shift(waveform: th.Tensor, n_steps, sample_rate: int = constant.SAMPLE_RATE, preserve_transients: bool = False) -> th.Tensor:
+def pitch_shift(waveform: th.Tensor, n_steps, sample_rate: int = constant.SAMPLE_RATE, preserve_transients: bool = False,
+                phase_lock: bool = False) -> th.Tensor:
     """torchaudio.functional.pitch_shift for a mono (samples,) waveform: with P / Q = pitch_ratio(n_steps), `time_stretch` by Q / P
     (longer for an upward shift), then `resample` from P to Q, cropped or zero-padded to the input's length.  The result does not
-    depend on `sample_rate` (kept for torchaudio's signature).  preserve_transients: passed to `time_stretch`."""
+    depend on `sample_rate` (kept for torchaudio's signature).  preserve_transients, phase_lock: passed to `time_stretch`."""
     f = pitch_ratio(n_steps)
     pv_ops.as_rate(1 / f)
-    y = time_stretch(waveform, 1 / f, preserve_transients=preserve_transients)
+    y = time_stretch(waveform, 1 / f, preserve_transients=preserve_transients, phase_lock=phase_lock)
     y = resample(y, f.numerator, f.denominator)
     n = waveform.shape[0]
     if y.shape[0] >= n:

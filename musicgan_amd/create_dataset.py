@@ -20,6 +20,9 @@ corpus.  Without them nothing changes.
 does: the harmonic part of the spectrum (audio.hpss) through the phase vocoder, the percussive part by overlap-add, so that drum hits
 are not smeared; the variant has the same number of frames either way.  `component` ("harmonic" or "percussive") replaces every
 spectrum about to be coded, the original's and each variant's, by that component of it.  Without the two nothing changes.
+`phase_lock` (with `stretch` / `pitch` only) sends the variants through the phase-locked vocoder (audio.phase_vocoder(...,
+phase_lock=True): the bins of one partial keep their phase differences, so moving pitches do not warble); the frame counts are the
+same.  Without it nothing changes.
 A single-process run records in the side-car which samples are consecutive chunks of one spectrum ("tracks": a file's own samples
 are one, each variant another): what training with random time offsets (`train --random-offset`) cuts its windows from.
 """
@@ -91,6 +94,14 @@ def check_separation(component=None, preserve_transients=False, rates=(), ratios
         raise ValueError(f"preserve_transients must be True or False, got {preserve_transients!r}")
     if preserve_transients and not (rates or ratios):
         raise ValueError("preserve_transients applies to the stretch / pitch variants: give at least one")
+
+
+def check_phase_lock(phase_lock=False, rates=(), ratios=()) -> None:
+    """ValueError for a phase_lock that is no bool and for phase_lock without a variant to apply it to -- host arithmetic"""
+    if not isinstance(phase_lock, bool):
+        raise ValueError(f"phase_lock must be True or False, got {phase_lock!r}")
+    if phase_lock and not (rates or ratios):
+        raise ValueError("phase_lock applies to the stretch / pitch variants: give at least one")
 
 
 def variant_counts(nb_frames_wav: int, nb_vec: int, rates=(), ratios=()) -> list:
@@ -351,7 +362,7 @@ class _Chunk:
 
 def create_dataset(audio_path: str, dataset_output_dir: str, *, packed: bool = True, writer_threads: int = 0,
                    stats: dict = None, resample: bool = False, stretch=(), pitch=(), component=None,
-                   preserve_transients: bool = False) -> None:
+                   preserve_transients: bool = False, phase_lock: bool = False) -> None:
     """`packed` (extension, single-process runs): also write the float32 memory-mapped side-car the fast loader reads
     (audio/dataset.py); the reference-format `magn_phase_{idx}.pt` files are written either way.  `writer_threads`: 0 = one per
     available CPU (at most 16).  `resample`: files not at 44.1 kHz are resampled to it (else they raise, as in the reference).
@@ -359,9 +370,12 @@ def create_dataset(audio_path: str, dataset_output_dir: str, *, packed: bool = T
     samples every file also yields, in the order given, those of its STFT re-timed by each rate, then those of its mono 44.1 kHz
     signal resampled by P / Q = audio.pitch_ratio(value) and re-timed by Q / P.  `preserve_transients`: the variants are re-timed
     with their percussive part overlap-added instead of going through the phase vocoder (a file of fewer than 4 frames raises
-    audio.istft's ValueError).  `component`: "harmonic" or "percussive", what audio.hpss leaves of every spectrum is coded."""
+    audio.istft's ValueError).  `component`: "harmonic" or "percussive", what audio.hpss leaves of every spectrum is coded.
+    `phase_lock` (with `stretch` / `pitch` only): the variants go through the phase-locked vocoder (audio.phase_vocoder(...,
+    phase_lock=True)); with `preserve_transients` their harmonic part does."""
     rates, ratios = check_variants(stretch, pitch)
     check_separation(component, preserve_transients, rates, ratios)
+    check_phase_lock(phase_lock, rates, ratios)
     w_p = glob.glob(audio_path)
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:
@@ -452,11 +466,15 @@ def create_dataset(audio_path: str, dataset_output_dir: str, *, packed: bool = T
 
                 def retime(spectrum, r):
                     if not preserve_transients:
+                        if phase_lock:
+                            return pv_ops.phase_vocoder(spectrum, r.numerator, r.denominator, lock=True)
                         return pv_ops.phase_vocoder(spectrum, r.numerator, r.denominator)
                     if spectrum.size()[1] < 4:
                         audio.istft(spectrum)  # raises: nothing that short can be separated and overlap-added
                     if pv_ops.phase_vocoder_len(spectrum.size()[1], r.numerator, r.denominator) - 1 < nb_vec:
                         return None  # too short for one image: left out below, as the plain variant would be
+                    if phase_lock:
+                        return audio.functions.retime_preserving_transients(spectrum, r, phase_lock=True)
                     return audio.functions.retime_preserving_transients(spectrum, r)
                 spectra += [retime(complex_values, r) for r in rates]
                 if ratios:

@@ -147,6 +147,215 @@ __global__ void __launch_bounds__(256) pv_finish(const float2* __restrict__ P, c
   out[(size_t)k * (size_t)n + (size_t)t] = float2{(float)(mag * (sign * re)), (float)(mag * (sign * im))};
 }
 
+// ---------------------------------------------------------------- identity phase locking ("Phase locking")
+// Output frame t picks peaks of its interpolated magnitude; every bin k follows the peak P = P_t(k) nearest to it:
+//   s_t[k] = s_{t-1}[P] + c_t(k),  c_t(k) = dev[P, t-1] + (arg X[k, i0] - arg X[P, i0]),  m4_t[k] = (m4_{t-1}[P] + P) mod 4,
+//   out = mag e^{i wrap(s_t[k])} i^(m4_t[k]);  frame 0: s = arg X[k, 0], m4 = 0 (stored as the step P = k, c = arg X[k, 0], no turn).
+// One frame is the map new[k] = old[P(k)] + c(k); such maps compose: (P2, c2) o (P1, c1) = (P1[P2], c1[P2] + c2).  Behind pv_polar:
+//   pvl_prepare   a workgroup = LOCK_PREP output frames x 512 bins: the polar rows those frames read go through LDS (lanes along
+//                 time on the way in, along frequency from there on); mag, the peaks, P, c, written time-major
+//   pvl_tile_map  a workgroup = LOCK_TILE output frames: the composed map of the tile (P int16, c float64, quarter turns), ping-pong in LDS
+//   pvl_carry     one workgroup, tile after tile: the state every tile starts from
+//   pvl_finish    the tiles again from that state; sine / cosine; the stores go back to frequency-major through LDS
+// Lanes are bins in all four; one barrier per frame; every sum has one order.
+constexpr int LOCK_TILE = 256;  // output frames per workgroup of pvl_tile_map / pvl_finish (pv_ops.LOCK_TILE)
+constexpr int LOCK_PREP = 4;    // output frames per workgroup of pvl_prepare (its LDS, 49 KB, lets three workgroups share a CU)
+constexpr int LOCK_ITEMS = 2 * (LOCK_PREP + 1);  // staged polar columns: the pairs (i0, i0 + 1) of frames t0 - 1 .. t0 + LOCK_PREP - 1
+constexpr int LOCK_PAD = NB + 1;                 // LDS row pitch of the staged columns
+constexpr int LOCK_FLUSH = 16;                   // output frames that pvl_finish collects before it stores them
+
+__global__ void __launch_bounds__(NB) pvl_prepare(const float2* __restrict__ Pol, short* __restrict__ pi, double* __restrict__ cs,
+                                                  double* __restrict__ mags, i64 T, i64 n, i64 p, i64 q) {
+  __shared__ float2 stage[LOCK_ITEMS * LOCK_PAD];
+  __shared__ double magbuf[2][NB];
+  __shared__ unsigned long long masks[2][NB / 64];
+  __shared__ i64 i0s[LOCK_PREP + 1];
+  __shared__ double alphas[LOCK_PREP + 1];
+  const int k = threadIdx.x;
+  const i64 t0 = (i64)blockIdx.x * LOCK_PREP;
+  if (k <= LOCK_PREP) {
+    const i64 t = t0 - 1 + k;
+    i64 i0 = -1;
+    double alpha = 0.0;
+    if (t >= 0 && t < n) {
+      const i64 tp = t * p;
+      i0 = tp / q;  // i0 <= T - 1 for every t < n
+      alpha = (double)(tp - i0 * q) / (double)q;
+    }
+    i0s[k] = i0;
+    alphas[k] = alpha;
+  }
+  __syncthreads();
+  for (int idx = k; idx < NB * LOCK_ITEMS; idx += NB) {  // LOCK_ITEMS neighbouring lanes read one row's columns
+    const int row = idx / LOCK_ITEMS, item = idx - row * LOCK_ITEMS;
+    const i64 i0 = i0s[item >> 1], i = i0 + (item & 1);
+    float2 v = float2{0.f, 0.f};  // frames T and T + 1 are zero (pv_polar never writes them)
+    if (i0 >= 0 && i < T) v = Pol[(size_t)row * (size_t)T + (size_t)i];
+    stage[item * LOCK_PAD + row] = v;
+  }
+  __syncthreads();
+  const int wave = k >> 6, lane = k & 63;
+  for (int f = 0; f < LOCK_PREP; ++f) {
+    const i64 t = t0 + f;
+    if (t >= n) break;
+    const int b = f & 1;
+    const float2 c0 = stage[(2 * f + 2) * LOCK_PAD + k], c1 = stage[(2 * f + 3) * LOCK_PAD + k];
+    const double alpha = alphas[f + 1];
+    const double mag = __dadd_rn(__dmul_rn(alpha, (double)c1.x), __dmul_rn(1.0 - alpha, (double)c0.x));
+    magbuf[b][k] = mag;
+    __syncthreads();
+    bool peak = mag > 0.0;
+    if (k >= 1) peak = peak && mag > magbuf[b][k - 1];
+    if (k >= 2) peak = peak && mag > magbuf[b][k - 2];
+    if (k + 1 < NB) peak = peak && mag >= magbuf[b][k + 1];
+    if (k + 2 < NB) peak = peak && mag >= magbuf[b][k + 2];
+    const unsigned long long mine = __ballot(peak);
+    if (lane == 0) masks[b][wave] = mine;
+    __syncthreads();
+    int lo = -1, hi = -1;  // the nearest peak at or below k, at or above k
+    unsigned long long m = mine & (lane == 63 ? ~0ull : ((2ull << lane) - 1ull));
+    for (int w = wave; w >= 0; --w) {
+      if (w != wave) m = masks[b][w];
+      if (m) {
+        lo = 64 * w + 63 - __clzll((long long)m);
+        break;
+      }
+    }
+    m = mine & (~0ull << lane);
+    for (int w = wave; w < NB / 64; ++w) {
+      if (w != wave) m = masks[b][w];
+      if (m) {
+        hi = 64 * w + __ffsll((long long)m) - 1;
+        break;
+      }
+    }
+    int P = k;  // no peak in the frame: the unlocked rule
+    if (lo >= 0 && hi >= 0) P = (k - lo <= hi - k) ? lo : hi;  // a tie goes to the lower peak
+    else if (lo >= 0) P = lo;
+    else if (hi >= 0) P = hi;
+    double c = (double)c0.y;  // frame 0: the state starts as arg X[k, 0]
+    if (t > 0) {  // dev[P, t - 1] from the pair of frame t - 1
+      const double dev = pv_wrap(((double)stage[(2 * f + 1) * LOCK_PAD + P].y - (double)stage[(2 * f) * LOCK_PAD + P].y) - (double)(P & 3) * PI_2);
+      c = dev + ((double)c0.y - (double)stage[(2 * f + 2) * LOCK_PAD + P].y);
+    }
+    const size_t at = (size_t)t * NB + k;
+    pi[at] = (short)(t > 0 ? P : k);
+    cs[at] = c;
+    mags[at] = mag;
+  }
+}
+
+// the composed map of every tile but the last: state_end[k] = state_start[Pi[k]] + C[k], turns likewise
+__global__ void __launch_bounds__(NB) pvl_tile_map(const short* __restrict__ pi, const double* __restrict__ cs, short* __restrict__ sumPi,
+                                                   double* __restrict__ sumC, unsigned char* __restrict__ sumM, i64 n) {
+  __shared__ double C[2][NB];
+  __shared__ short Pi[2][NB];
+  __shared__ unsigned char M[2][NB];
+  const int k = threadIdx.x;
+  const i64 t0 = (i64)blockIdx.x * LOCK_TILE, t1 = (t0 + LOCK_TILE < n) ? t0 + LOCK_TILE : n;
+  C[0][k] = 0.0;
+  Pi[0][k] = (short)k;
+  M[0][k] = 0;
+  __syncthreads();
+  size_t at = (size_t)t0 * NB + k;
+  int P = pi[at], cur = 0;
+  double c = cs[at];
+  for (i64 t = t0; t < t1; ++t) {
+    int Pn = 0;
+    double cn = 0.0;
+    if (t + 1 < t1) {  // the next frame's step is on its way while this one waits at the barrier
+      Pn = pi[at + NB];
+      cn = cs[at + NB];
+    }
+    C[cur ^ 1][k] = C[cur][P] + c;
+    Pi[cur ^ 1][k] = Pi[cur][P];
+    M[cur ^ 1][k] = (unsigned char)((M[cur][P] + (t > 0 ? P : 0)) & 3);
+    __syncthreads();
+    cur ^= 1;
+    P = Pn;
+    c = cn;
+    at += NB;
+  }
+  const size_t o = (size_t)blockIdx.x * NB + k;
+  sumPi[o] = Pi[cur][k];
+  sumC[o] = C[cur][k];
+  sumM[o] = M[cur][k];
+}
+
+__global__ void __launch_bounds__(NB) pvl_carry(const short* __restrict__ sumPi, const double* __restrict__ sumC,
+                                                const unsigned char* __restrict__ sumM, double* __restrict__ startS,
+                                                unsigned char* __restrict__ startM, int ntiles) {
+  __shared__ double S[2][NB];
+  __shared__ unsigned char M[2][NB];
+  const int k = threadIdx.x;
+  S[0][k] = 0.0;
+  M[0][k] = 0;
+  __syncthreads();
+  int cur = 0;
+  for (int j = 0; j < ntiles; ++j) {
+    const size_t o = (size_t)j * NB + k;
+    startS[o] = S[cur][k];
+    startM[o] = M[cur][k];
+    if (j + 1 == ntiles) break;  // the last tile has no summary
+    const int P = sumPi[o];
+    S[cur ^ 1][k] = S[cur][P] + sumC[o];
+    M[cur ^ 1][k] = (unsigned char)((M[cur][P] + sumM[o]) & 3);
+    __syncthreads();
+    cur ^= 1;
+  }
+}
+
+__global__ void __launch_bounds__(NB) pvl_finish(const short* __restrict__ pi, const double* __restrict__ cs, const double* __restrict__ mags,
+                                                 const double* __restrict__ startS, const unsigned char* __restrict__ startM,
+                                                 float2* __restrict__ out, i64 n) {
+  __shared__ double S[2][NB];
+  __shared__ unsigned char M[2][NB];
+  __shared__ float2 rows[NB * (LOCK_FLUSH + 1)];
+  const int k = threadIdx.x;
+  const i64 t0 = (i64)blockIdx.x * LOCK_TILE, t1 = (t0 + LOCK_TILE < n) ? t0 + LOCK_TILE : n;
+  S[0][k] = startS[(size_t)blockIdx.x * NB + k];
+  M[0][k] = startM[(size_t)blockIdx.x * NB + k];
+  __syncthreads();
+  size_t at = (size_t)t0 * NB + k;
+  int P = pi[at], cur = 0;
+  double c = cs[at], mag = mags[at];
+  for (i64 t = t0; t < t1; ++t) {
+    int Pn = 0;
+    double cn = 0.0, magn = 0.0;
+    if (t + 1 < t1) {
+      Pn = pi[at + NB];
+      cn = cs[at + NB];
+      magn = mags[at + NB];
+    }
+    const double s = S[cur][P] + c;
+    const int m4 = (M[cur][P] + (t > 0 ? P : 0)) & 3;
+    S[cur ^ 1][k] = s;
+    M[cur ^ 1][k] = (unsigned char)m4;
+    int quad;
+    double sn, cn2;
+    pv_sincos(pv_wrap(s), quad, sn, cn2);
+    const int turns = (quad + m4) & 3;  // e^{i r} i^turns
+    const double re = (turns & 1) ? -sn : cn2, im = (turns & 1) ? cn2 : sn;
+    const double sign = (turns & 2) ? -1.0 : 1.0;
+    const int g = (int)(t - t0) % LOCK_FLUSH;
+    rows[k * (LOCK_FLUSH + 1) + g] = float2{(float)(mag * (sign * re)), (float)(mag * (sign * im))};
+    __syncthreads();
+    if (g == LOCK_FLUSH - 1 || t + 1 == t1) {  // LOCK_FLUSH neighbouring lanes store one row's run of frames
+      const i64 tb = t - g;
+      for (int idx = k; idx < NB * LOCK_FLUSH; idx += NB) {
+        const int row = idx / LOCK_FLUSH, gg = idx % LOCK_FLUSH;
+        if (gg <= g) out[(size_t)row * (size_t)n + (size_t)(tb + gg)] = rows[row * (LOCK_FLUSH + 1) + gg];
+      }
+      __syncthreads();  // `rows` is written again by the next frame
+    }
+    cur ^= 1;
+    P = Pn;
+    c = cn;
+    mag = magn;
+    at += NB;
+  }
+}
+
 // 0: fine; else the reason
 const char* bad_rate(i64 frames, int p, int q) {
   if (p < 1 || q < 1) return "p and q must be at least 1";
@@ -157,6 +366,29 @@ const char* bad_rate(i64 frames, int p, int q) {
 }
 
 size_t polar_bytes(i64 frames) { return (((size_t)NB * (size_t)frames * sizeof(float2)) + 15) / 16 * 16; }
+
+// the locked vocoder's workspace behind the polar rows, widest elements first (every part a multiple of 16 bytes)
+struct LockLayout {
+  size_t c, mag, sumC, startS, pi, sumPi, sumM, startM, total;
+  int ntiles;
+};
+
+LockLayout lock_layout(i64 frames, i64 n) {
+  LockLayout L;
+  L.ntiles = (int)((n + LOCK_TILE - 1) / LOCK_TILE);
+  const size_t bins = (size_t)NB * (size_t)n, tiles = (size_t)NB * (size_t)L.ntiles;
+  size_t at = polar_bytes(frames);
+  L.c = at, at += bins * sizeof(double);
+  L.mag = at, at += bins * sizeof(double);
+  L.sumC = at, at += tiles * sizeof(double);
+  L.startS = at, at += tiles * sizeof(double);
+  L.pi = at, at += bins * sizeof(short);
+  L.sumPi = at, at += tiles * sizeof(short);
+  L.sumM = at, at += tiles;
+  L.startM = at, at += tiles;
+  L.total = at;
+  return L;
+}
 
 }  // namespace
 
@@ -201,5 +433,55 @@ extern "C" int mg_phase_vocoder(const float* x_c64, float* out_c64, void* ws, si
   hipLaunchKernelGGL(pv_finish, dim3(ntiles, NB), dim3(TILE), 0, s, P, sums, reinterpret_cast<float2*>(out_c64), T, n, (i64)p, (i64)q,
                      ntiles);
   MG_CHECK_LAUNCH("mg_phase_vocoder(finish)");
+  return MG_OK;
+}
+
+extern "C" size_t mg_phase_vocoder_locked_ws_bytes(int64_t frames, int p, int q) {
+  const int64_t n = mg_phase_vocoder_len(frames, p, q);
+  if (n < 1 || n >= ((int64_t)1 << 31) - TILE || frames >= ((int64_t)1 << 31)) return 0;
+  return lock_layout(frames, n).total;
+}
+
+extern "C" int mg_phase_vocoder_locked(const float* x_c64, float* out_c64, void* ws, size_t ws_bytes, int64_t frames, int p, int q,
+                                       mg_stream_t stream) {
+  MG_CHECK_ARG(x_c64 && out_c64 && ws, "mg_phase_vocoder_locked: bad arguments");
+  const char* why = bad_rate(frames, p, q);
+  MG_CHECK_ARG(!why, "mg_phase_vocoder_locked: %s (got frames %lld, p %d, q %d)", why, (long long)frames, p, q);
+  const i64 T = frames, n = mg_phase_vocoder_len(frames, p, q);
+  MG_CHECK_ARG(T < ((i64)1 << 31) && n < ((i64)1 << 31) - TILE, "mg_phase_vocoder_locked: input and output must stay below 2^31 frames");
+  MG_CHECK_ARG((reinterpret_cast<uintptr_t>(x_c64) | reinterpret_cast<uintptr_t>(out_c64)) % 8 == 0 &&
+               reinterpret_cast<uintptr_t>(ws) % 16 == 0,
+               "mg_phase_vocoder_locked: the spectra must be 8-byte aligned, the workspace 16-byte aligned");
+  if (ws_bytes < mg_phase_vocoder_locked_ws_bytes(frames, p, q)) {
+    mg_set_error("mg_phase_vocoder_locked: workspace too small");
+    return MG_EWORKSPACE;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const LockLayout L = lock_layout(T, n);
+  char* base = reinterpret_cast<char*>(ws);
+  float2* P = reinterpret_cast<float2*>(ws);
+  double* cs = reinterpret_cast<double*>(base + L.c);
+  double* mags = reinterpret_cast<double*>(base + L.mag);
+  double* sumC = reinterpret_cast<double*>(base + L.sumC);
+  double* startS = reinterpret_cast<double*>(base + L.startS);
+  short* pi = reinterpret_cast<short*>(base + L.pi);
+  short* sumPi = reinterpret_cast<short*>(base + L.sumPi);
+  unsigned char* sumM = reinterpret_cast<unsigned char*>(base + L.sumM);
+  unsigned char* startM = reinterpret_cast<unsigned char*>(base + L.startM);
+  const int sparse = (i64)p >= 2 * (i64)q;
+  const i64 items = sparse ? 2 * n : T;
+  hipLaunchKernelGGL(pv_polar, dim3((unsigned)((items + 255) / 256), NB), dim3(256), 0, s, reinterpret_cast<const float2*>(x_c64), P, T,
+                     n, (i64)p, (i64)q, sparse);
+  MG_CHECK_LAUNCH("mg_phase_vocoder_locked(polar)");
+  hipLaunchKernelGGL(pvl_prepare, dim3((unsigned)((n + LOCK_PREP - 1) / LOCK_PREP)), dim3(NB), 0, s, P, pi, cs, mags, T, n, (i64)p, (i64)q);
+  MG_CHECK_LAUNCH("mg_phase_vocoder_locked(prepare)");
+  if (L.ntiles > 1) {  // the last tile's map is needed by nobody
+    hipLaunchKernelGGL(pvl_tile_map, dim3(L.ntiles - 1), dim3(NB), 0, s, pi, cs, sumPi, sumC, sumM, n);
+    MG_CHECK_LAUNCH("mg_phase_vocoder_locked(tile map)");
+  }
+  hipLaunchKernelGGL(pvl_carry, dim3(1), dim3(NB), 0, s, sumPi, sumC, sumM, startS, startM, L.ntiles);
+  MG_CHECK_LAUNCH("mg_phase_vocoder_locked(carry)");
+  hipLaunchKernelGGL(pvl_finish, dim3(L.ntiles), dim3(NB), 0, s, pi, cs, mags, startS, startM, reinterpret_cast<float2*>(out_c64), n);
+  MG_CHECK_LAUNCH("mg_phase_vocoder_locked(finish)");
   return MG_OK;
 }

@@ -13,6 +13,7 @@ from ._lib import check
 from .ops import _p, _s
 
 TIME_TILE = 256                                  # output frames per workgroup (TILE of csrc/phasevocoder.hip)
+LOCK_TILE = 256                                  # output frames per composed map of the locked vocoder (LOCK_TILE there)
 MIN_RATE, MAX_RATE = Fraction(1, 8), Fraction(8)
 
 
@@ -55,10 +56,14 @@ def phase_vocoder_len(frames: int, p: int, q: int) -> int:
     return n
 
 
-def phase_vocoder(X: torch.Tensor, p: int, q: int) -> torch.Tensor:
+def phase_vocoder(X: torch.Tensor, p: int, q: int, lock: bool = False) -> torch.Tensor:
     """X complex64 (512, T), rate p / q in [1/8, 8] -> complex64 (512, ceil(T q / p)): torchaudio.functional.phase_vocoder with
     phase_advance pi k / 2 (hop 256 of 1024), magnitudes and angles in float32 as torch takes them, the phase accumulated in float64
-    modulo 2 pi; four launches (`mg_phase_vocoder`)"""
+    modulo 2 pi; four launches (`mg_phase_vocoder`).  lock: identity phase locking (Laroche & Dolson 1999) -- every bin follows
+    the nearest magnitude peak of its output frame and keeps the analysis frame's phase difference against it, so the bins of
+    one partial stay together; five launches (`mg_phase_vocoder_locked`)"""
+    if not isinstance(lock, bool):
+        raise ValueError(f"lock must be True or False, got {lock!r}")
     if X.dim() != 2 or X.shape[0] != 512 or X.shape[1] < 1:
         raise ValueError(f"a (512, T >= 1) spectrum expected, got {tuple(X.shape)}")
     frames = X.shape[1]
@@ -69,10 +74,12 @@ def phase_vocoder(X: torch.Tensor, p: int, q: int) -> torch.Tensor:
         raise _lib.MusicGanHipError(f"phase_vocoder: contiguous complex64 expected, got {X.dtype} contiguous={X.is_contiguous()}")
     lib = _lib.load()
     n = phase_vocoder_len(frames, p, q)
-    nbytes = int(lib.mg_phase_vocoder_ws_bytes(frames, p, q))
+    ws_bytes, run, what = ((lib.mg_phase_vocoder_locked_ws_bytes, lib.mg_phase_vocoder_locked, "mg_phase_vocoder_locked") if lock else
+                           (lib.mg_phase_vocoder_ws_bytes, lib.mg_phase_vocoder, "mg_phase_vocoder"))
+    nbytes = int(ws_bytes(frames, p, q))
     if nbytes == 0:
         raise ValueError(f"phase_vocoder: {frames} frames at rate {p}/{q} are too many (2^31 frames and more)")
     ws = ops.workspace(nbytes, X.device)
     out = torch.empty((512, n, 2), dtype=torch.float32, device=X.device)
-    check(lib.mg_phase_vocoder(_p(X), _p(out), _p(ws), nbytes, frames, p, q, _s()), "mg_phase_vocoder")
+    check(run(_p(X), _p(out), _p(ws), nbytes, frames, p, q, _s()), what)
     return torch.view_as_complex(out)
