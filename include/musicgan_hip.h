@@ -866,6 +866,28 @@ int mg_hpss(const float* x_c64, float* harm_c64, float* perc_c64, float* H, floa
             int lh, int lp, float power, float margin_h, float margin_p, mg_stream_t stream);
 int mg_ola_stretch(const float* x, int64_t length, float* y, int64_t out_length, int p, int q, mg_stream_t stream);
 
+/* ---- log-mel feature rows and float64 moments (csrc/logmel.hip, csrc/moments.hip): the kernels behind musicgan_amd/mel_ops.py,
+ * metrics.LogMel and metrics.Frechet, which the reference does not have (definition: DESIGN.md 4.19).
+ * logmel_rows: x (n, channels, h, w) float32, rows = frequency, columns = time; scale (h,), weight (bands, h) float32 on the device;
+ *   lo, hi: HOST arrays of `bands` row limits, 0 <= lo <= hi <= h, read before the call returns and passed to the kernel by value
+ *   (MG_EINVAL otherwise: no row index depends on device memory); bands <= 256; `pools` divides w, w / pools <= 1024; floor > 0.
+ *     p[h,t] = (x[i,c,h,t] scale[h] + scale[h])^2                  float32, every operation rounded
+ *     s[m,t] = sum_{h = lo[m]}^{hi[m]-1} weight[m,h] p[h,t]         float32, ascending h, product and sum rounded apart
+ *     v[m,t] = log((double)s[m,t] + floor)                          float64
+ *     out[i, m pools + j] = (float)(sum of v[m,t] over the w / pools columns of pool j in ascending t, / (w / pools))
+ *   out (n, bands pools) float32, every element written; weights outside [lo, hi) are not read.  One launch per 32 768 images on
+ *   `stream`, no workspace, no atomics, capturable.  A row of out depends on its image and on the shapes alone.
+ * moments_ws_bytes: HOST query, the float64 partial sums of mg_moments: ceil(n / 1024) x (d + d d) x 8 (0: the shape is refused).
+ * moments: rows (n, d) float32, 2 <= n <= 2^24, 1 <= d <= 4096 -> mean (d,) and cov (d, d) float64, two passes in float64:
+ *     mean_j = (sum_i x_ij) / n;   cov_jk = sum_i (x_ij - mean_j)(x_ik - mean_k) / (n - 1)
+ *   Sums run over chunks of 1024 rows in ascending order from +0.0 and the chunk sums are added in chunk order: the same bits in every
+ *   run.  All of cov is written and cov[j,k] and cov[k,j] hold the same bits.  Four launches on `stream`, no atomics, capturable; ws
+ *   at an 8-byte boundary; the part of it that is read was written by the same call. */
+int mg_logmel_rows(const float* x, int n, int channels, int c, int h, int w, const float* scale, const float* weight,
+                   const int32_t* lo, const int32_t* hi, int bands, double floor, int pools, float* out, mg_stream_t stream);
+size_t mg_moments_ws_bytes(int64_t n, int64_t d);
+int mg_moments(const float* rows, int64_t n, int64_t d, double* mean, double* cov, void* ws, size_t ws_bytes, mg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,5 @@
 """`python -m musicgan_amd <mode> ...`: the reference's four sub-commands with its positional names and flags
-(/root/reference/music_gan/__main__.py:11-124) and `evaluate`, `loudness`, `separate` and `project`, which the reference does not have, declared as data and dispatched
+(/root/reference/music_gan/__main__.py:11-124) and `evaluate`, `loudness`, `separate`, `project` and `evaluate_mel`, which the reference does not have, declared as data and dispatched
 lazily (importing `train` pulls in the GPU library, `view_audio` pulls in matplotlib)."""
 import argparse
 import importlib
@@ -9,6 +9,7 @@ from fractions import Fraction
 _METRICS = ("swd", "msssim", "nn")
 _METRICS_ALL = _METRICS + ("prdc",)
 _METRICS_EVERY = _METRICS_ALL + ("ndb",)
+_MEL_METRICS = ("fd", "nn", "prdc", "ndb")   # evaluate_mel.METRICS
 _AUGMENTS = ("translation", "cutout")   # aug_ops.OPS (not imported here: the modes are dispatched lazily)
 
 
@@ -16,6 +17,13 @@ def _metric_list(text: str):
     names = tuple(t.strip() for t in text.split(","))
     if any(n not in _METRICS_EVERY for n in names) or len(set(names)) != len(names):
         raise argparse.ArgumentTypeError(f"a comma-separated subset of {','.join(_METRICS_EVERY)} expected, got {text!r}")
+    return names
+
+
+def _mel_metric_list(text: str):
+    names = tuple(t.strip() for t in text.split(","))
+    if any(n not in _MEL_METRICS for n in names) or len(set(names)) != len(names):
+        raise argparse.ArgumentTypeError(f"a comma-separated subset of {','.join(_MEL_METRICS)} expected, got {text!r}")
     return names
 
 
@@ -209,10 +217,30 @@ _LATENT_MODES = {
                        **({"griffin_lim": a.griffin_lim} if a.griffin_lim else {}),
                        **({"resample": True} if a.resample else {}))),
 }
+# sub-commands that evaluate a checkpoint in a feature space other than pixels (same declaration; kept apart as well)
+_FEATURE_MODES = {
+    "evaluate_mel": ("evaluate_mel", "evaluate_mel", [
+        (("gen_dict_state",), dict(type=str)),
+        (("rand_channels",), dict(type=int)),
+        (("-i", "--input-dataset"), dict(dest="input_dataset", type=str, required=True)),
+        (("--level",), dict(type=int, default=7, help="growth level of the checkpoint, 4 .. 7 (7: fully grown, 512 x 512)")),
+        (("-n", "--nb-images"), dict(dest="nb_images", type=int, default=8192, help="images per set (clipped to the dataset)")),
+        (("--batch-size",), dict(dest="batch_size", type=int, default=16)),
+        (("--seed",), dict(type=int, default=0)),
+        (("-o", "--output"), dict(type=str, default=None, help="also write the result as JSON to this file")),
+        (("--metrics",), dict(type=_mel_metric_list, default=None, metavar="fd,nn,prdc,ndb",
+                              help="what to report in the log-mel spectrogram of what the images decode to (default: fd); fd: the "
+                                   "Frechet distance between the Gaussians fitted to the generated and to the real rows, with "
+                                   "fd_half and fd_real at equal set sizes -- fd_half near fd_real is what a perfect generator "
+                                   "scores; nn, prdc, ndb: as in evaluate, on log-mel rows instead of pixels")),
+    ], lambda a: (a.gen_dict_state, a.rand_channels, a.input_dataset),
+        lambda a: dict(level=a.level, nb_images=a.nb_images, batch_size=a.batch_size, seed=a.seed, output=a.output,
+                       **({"metrics": a.metrics} if a.metrics is not None else {}))),
+}
 
 
 def _all_modes() -> dict:
-    return {**_MODES, **_FILE_MODES, **_LATENT_MODES}
+    return {**_MODES, **_FILE_MODES, **_LATENT_MODES, **_FEATURE_MODES}
 
 
 def build_parser() -> argparse.ArgumentParser:

@@ -250,6 +250,10 @@ SIGNATURES = {
     "mg_pyramid_l2": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), _P, _P, _P, c_size_t, _P]),
     "mg_hpss": (c_int, [_P] * 7 + [c_int64, c_int, c_int, c_float, c_float, c_float, _P]),
     "mg_ola_stretch": (c_int, [_P, c_int64, _P, c_int64, c_int, c_int, _P]),
+    "mg_logmel_rows": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, POINTER(ctypes.c_int32), POINTER(ctypes.c_int32), c_int,
+                               ctypes.c_double, c_int, _P, _P]),
+    "mg_moments_ws_bytes": (c_size_t, [c_int64, c_int64]),
+    "mg_moments": (c_int, [_P, c_int64, c_int64, _P, _P, _P, c_size_t, _P]),
 }
 
 _lib = None

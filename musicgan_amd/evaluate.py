@@ -46,6 +46,9 @@ class _Images:
     def __init__(self, dataset, gen, latents: torch.Tensor, side: int, batch_size: int) -> None:
         self.dataset, self.gen, self.latents, self.device = dataset, gen, latents, latents.device
         self.side, self.cside, self.batch_size = side, min(side, _NN_SIDE), batch_size
+        # the space the kNN metrics compare in: how the printed lines name it, what a row is called, the numbers in a row
+        self.space, self.row_what = f"at {self.cside} x {self.cside}", f"images of {self.cside} x {self.cside}"
+        self.row_numel = 2 * self.cside * self.cside
 
     def real(self, indices) -> torch.Tensor:
         return ops.input_transform(torch.stack([self.dataset[i] for i in indices]).to(self.device).contiguous(), self.side)
@@ -58,7 +61,7 @@ class _Images:
             return self.gen(self.latents[rows].contiguous(), 1.0).contiguous()
 
     def reduced(self, x: torch.Tensor) -> torch.Tensor:
-        """at most _NN_SIDE pixels a side, by 2 x 2 means"""
+        """the rows the kNN metrics compare: here at most _NN_SIDE pixels a side, by 2 x 2 means"""
         while x.shape[-1] > self.cside:
             x = ops.avgpool2_fwd(x)
         return x
@@ -70,9 +73,9 @@ class _Images:
 
 
 def _check_resident(images: _Images, count: int, what: str) -> None:
-    need, free = count * 2 * images.cside * images.cside * 4, torch.cuda.mem_get_info(images.device)[0]
+    need, free = count * images.row_numel * 4, torch.cuda.mem_get_info(images.device)[0]
     if need > 0.75 * free:
-        raise ValueError(f"{what} images of {images.cside} x {images.cside} resident: {need} bytes, more than three quarters of the "
+        raise ValueError(f"{what} {images.row_what} resident: {need} bytes, more than three quarters of the "
                          f"{free} bytes free on the device")
 
 
@@ -106,7 +109,7 @@ def _msssim(images: _Images, nb_images: int, perm, seed: int) -> Dict[str, float
 
 
 def _nn(images: _Images, nb_images: int, perm, seed: int) -> Dict[str, float]:
-    nq, cside = min(nb_images, _NN_QUERIES), images.cside
+    nq = min(nb_images, _NN_QUERIES)
     fake_q = torch.cat([images.reduced(images.fake(slice(lo, lo + images.batch_size)))   # whole batches, cut to nq afterwards
                         for lo, _ in images.batches(nq)])[:nq].contiguous()
     real_q = torch.cat([images.reduced(images.real(perm[lo:hi])) for lo, hi in images.batches(nq)])
@@ -124,14 +127,14 @@ def _nn(images: _Images, nb_images: int, perm, seed: int) -> Dict[str, float]:
         for name in ("fake", "real"):
             result[f"nn_{name}{suffix}"] = float(fn(rms[name]))
     for name in ("fake", "real"):
-        print(f"NN RMS [{name}] = {result['nn_' + name]:.6f} (smallest {result['nn_' + name + '_min']:.6f}) at {cside} x {cside}")
+        print(f"NN RMS [{name}] = {result['nn_' + name]:.6f} (smallest {result['nn_' + name + '_min']:.6f}) {images.space}")
     print("NN: fake well below real, or a smallest fake value near 0, means memorised training samples")
     return result
 
 
 def _prdc(images: _Images, nb_images: int, perm, seed: int) -> Dict[str, float]:
     _check_resident(images, 2 * nb_images, f"prdc keeps {nb_images} real and {nb_images} generated")
-    half, cside = nb_images // 2, images.cside
+    half = nb_images // 2
     prdc = PRDC(k=_PRDC_K)
     for lo, hi in images.batches(nb_images):
         prdc.feed_real(images.reduced(images.real(range(lo, hi))))
@@ -143,14 +146,14 @@ def _prdc(images: _Images, nb_images: int, perm, seed: int) -> Dict[str, float]:
         prdc.feed_fake(images.reduced(images.real(perm[half + lo:half + hi])))
     result.update({name + "_real": value for name, value in prdc.result().items()})
     for name in result:
-        print(f"PRDC [{name:>14}] = {result[name]:.6f} at {cside} x {cside}, k = {_PRDC_K}")
+        print(f"PRDC [{name:>14}] = {result[name]:.6f} {images.space}, k = {_PRDC_K}")
     print("PRDC: low precision means samples off the data manifold, low recall or coverage means modes missing; compare with "
           "the _real column (two halves of the data against each other)")
     return result
 
 
 def _ndb(images: _Images, nb_images: int, perm, seed: int) -> Dict[str, float]:
-    half, cside = nb_images // 2, images.cside
+    half = nb_images // 2
     bins = _ndb_bins(half)
     _check_resident(images, half, f"ndb keeps {half} real")
     km = KMeans(bins, iterations=_NDB_ITERATIONS, seed=seed)   # the bins: fitted on one random half of the real set
@@ -164,7 +167,7 @@ def _ndb(images: _Images, nb_images: int, perm, seed: int) -> Dict[str, float]:
     result = ndb_fake.result()
     result.update({name + "_real": value for name, value in ndb_real.result().items()})
     last = int(km.changed[-1])
-    print(f"NDB: {bins} k-means bins fitted on {half} real images at {cside} x {cside}; the last of {_NDB_ITERATIONS} iterations "
+    print(f"NDB: {bins} k-means bins fitted on {half} real images {images.space}; the last of {_NDB_ITERATIONS} iterations "
           f"changed {last} labels" + ("" if last == 0 else " (not converged: raise the iterations)"))
     if half < _NDB_PER_BIN * bins:
         print(f"NDB: fewer than {_NDB_PER_BIN} reference images per bin: the test has little power")
@@ -190,6 +193,33 @@ def _check_sizes(metrics: Sequence[str], nb_images: int) -> None:
     for name, (_, least, refusal) in _RUNNERS.items():
         if name in metrics and nb_images < least:
             raise ValueError(f"{refusal}, got {nb_images}")
+
+
+def _open(source, check_sizes, gen_dict_state: str, rand_channels: int, input_dataset: str, level: int, nb_images: int,
+          batch_size: int, seed: int):
+    """What every driver starts with: the generator, the dataset, one draw of latents and one seeded order of the dataset.
+    `source`: the _Images class to draw from; `check_sizes(n)` refuses an image count.  Returns (images, nb_images clipped to the
+    dataset, perm)."""
+    side = _FULL_SIDE >> (_FINAL_LEVEL - level)
+    device = torch.device("cuda", torch.cuda.current_device())
+
+    print("Load model...")
+    gen = Generator(rand_channels, end_layer=level)
+    gen.load_state_dict(torch.load(gen_dict_state, map_location="cpu"))
+    gen = gen.to(device).eval()
+
+    dataset = audio.PackedAudioDataset(input_dataset) if audio.has_packed(input_dataset) else audio.AudioDataset(input_dataset)
+    if nb_images > len(dataset):
+        print(f"The dataset holds {len(dataset)} samples: evaluating on {len(dataset)} images instead of {nb_images}")
+        nb_images = len(dataset)
+    check_sizes(nb_images)   # ... and for what the dataset holds
+
+    print(f"Evaluate {nb_images} real and {nb_images} generated images of {side} x {side}...")
+    rng = torch.Generator(device=device).manual_seed(seed)
+    # every latent in one draw (a few MB): the samples do not depend on the batch size
+    latents = torch.randn(nb_images, rand_channels, _LATENT_H, _LATENT_W, device=device, generator=rng)
+    perm = torch.randperm(nb_images, generator=torch.Generator().manual_seed(seed)).tolist()
+    return source(dataset, gen, latents, side, batch_size), nb_images, perm
 
 
 def evaluate(gen_dict_state: str, rand_channels: int, input_dataset: str, metrics: Sequence[str] = ("swd",), *,
@@ -229,26 +259,8 @@ def evaluate(gen_dict_state: str, rand_channels: int, input_dataset: str, metric
     if not metrics or any(m not in METRICS_EVERY for m in metrics) or len(set(metrics)) != len(metrics):
         raise ValueError(f"metrics: a non-empty subset of {METRICS_EVERY} expected, got {metrics}")
     _check_sizes(metrics, nb_images)   # before any work ...
-    side = _FULL_SIDE >> (_FINAL_LEVEL - level)
-    device = torch.device("cuda", torch.cuda.current_device())
-
-    print("Load model...")
-    gen = Generator(rand_channels, end_layer=level)
-    gen.load_state_dict(torch.load(gen_dict_state, map_location="cpu"))
-    gen = gen.to(device).eval()
-
-    dataset = audio.PackedAudioDataset(input_dataset) if audio.has_packed(input_dataset) else audio.AudioDataset(input_dataset)
-    if nb_images > len(dataset):
-        print(f"The dataset holds {len(dataset)} samples: evaluating on {len(dataset)} images instead of {nb_images}")
-        nb_images = len(dataset)
-    _check_sizes(metrics, nb_images)   # ... and for what the dataset holds
-
-    print(f"Evaluate {nb_images} real and {nb_images} generated images of {side} x {side}...")
-    rng = torch.Generator(device=device).manual_seed(seed)
-    # every latent in one draw (a few MB): the samples do not depend on the batch size
-    latents = torch.randn(nb_images, rand_channels, _LATENT_H, _LATENT_W, device=device, generator=rng)
-    perm = torch.randperm(nb_images, generator=torch.Generator().manual_seed(seed)).tolist()
-    images = _Images(dataset, gen, latents, side, batch_size)
+    images, nb_images, perm = _open(_Images, lambda n: _check_sizes(metrics, n), gen_dict_state, rand_channels, input_dataset, level,
+                                    nb_images, batch_size, seed)
     result = {}
     for name in METRICS_EVERY:
         if name in metrics:

@@ -49,7 +49,17 @@ csrc/kmeans.hip through musicgan_amd/km_ops.py, distances through nn_ops.nn_sqdi
     km.fit()                                      # launches only
     ndb = NDB(km)
     for batch in fake:  ndb.feed(batch)           # assigned and counted, not kept
-    ndb.result()                                  # {"ndb": share of statistically different bins, "jsd": of the two histograms}"""
+    ndb.result()                                  # {"ndb": share of statistically different bins, "jsd": of the two histograms}
+
+(6) A feature space other than pixels that needs no pretrained network: the log-mel spectrogram of what an image decodes to, and in
+it the Frechet distance between the Gaussians fitted to two sets (the formula of FID).  Definition: DESIGN.md 4.19; kernels:
+csrc/logmel.hip and csrc/moments.hip through musicgan_amd/mel_ops.py.
+
+    rows = LogMel(512, 512, pools=8)              # (B, 2, 512, 512) float32 cuda -> (B, 64 * 8) float32 cuda
+    fd = Frechet()
+    for batch in real:  fd.feed_real(rows(batch)) # any (B, ...) float32 cuda batch, any split
+    for batch in fake:  fd.feed_fake(rows(batch))
+    fd.result()                                   # float; fd.moments(): the float64 means and covariances, on the device"""
 from __future__ import annotations
 
 import math
@@ -58,7 +68,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
-from . import km_ops, nn_ops, ops, ssim_ops
+from . import km_ops, mel_ops, nn_ops, ops, ssim_ops
 
 
 def pyramid_sides(side_h: int, side_w: int, min_side: int = 16) -> List[Tuple[int, int]]:
@@ -739,3 +749,146 @@ class NDB:
         per = self.per_bin()
         st = ndb_statistics(per["reference"], per["query"])
         return {"ndb": st["ndb"], "jsd": st["jsd"]}
+
+
+# ------------------------------------------------------------------ log-mel feature space, Frechet distance
+_MEL_RATE, _MEL_BINS = 44100.0, 512   # the codec's sample rate and the STFT bins an image row stands for (N_FFT / 2)
+
+
+def mel_filterbank(rows: int, bands: int, f_min: float = 0.0, f_max: float = 22050.0):
+    """Triangular HTK mel filters over the rows of a magnitude image, in host float64.  `rows`: a power of two in
+    8 .. 512; with q = 512 // rows, row r stands for the STFT bins r q .. r q + q - 1 and has the frequency
+    f_r = (r q + (q - 1) / 2) * 44100 / 1024 Hz.  The bands + 2 points p are equally spaced on the mel scale
+    2595 log10(1 + f / 700) between f_min and f_max, and
+        w[m, r] = max(0, min((f_r - p_m) / (p_{m+1} - p_m), (p_{m+2} - f_r) / (p_{m+2} - p_{m+1})))
+    which is torchaudio.functional.melscale_fbanks(norm=None, mel_scale="htk") evaluated at those frequencies.  Returns (weight
+    float32 (bands, rows), lo int32 (bands,), hi int32 (bands,)) on the host: [lo, hi) is the tightest row range that holds a
+    band's non-zero weights.  A band without a non-zero weight raises ValueError (too many bands for so few rows)."""
+    if not _is_int(rows) or not 8 <= rows <= _MEL_BINS or rows & (rows - 1):
+        raise ValueError(f"rows: a power of two in 8 .. {_MEL_BINS} expected, got {rows}")
+    if not _is_int(bands) or bands < 1:
+        raise ValueError(f"bands >= 1 expected, got {bands}")
+    f_min, f_max = float(f_min), float(f_max)
+    if not 0.0 <= f_min < f_max <= _MEL_RATE / 2:
+        raise ValueError(f"0 <= f_min < f_max <= {_MEL_RATE / 2} expected, got {f_min}, {f_max}")
+    q = _MEL_BINS // rows
+    f = (torch.arange(rows, dtype=torch.float64) * q + (q - 1) / 2) * (_MEL_RATE / (2 * _MEL_BINS))
+    mel = torch.linspace(2595.0 * math.log10(1.0 + f_min / 700.0), 2595.0 * math.log10(1.0 + f_max / 700.0), bands + 2,
+                         dtype=torch.float64)
+    p = 700.0 * (torch.pow(10.0, mel / 2595.0) - 1.0)
+    up = (f[None, :] - p[:-2, None]) / (p[1:-1] - p[:-2])[:, None]
+    down = (p[2:, None] - f[None, :]) / (p[2:] - p[1:-1])[:, None]
+    w = torch.minimum(up, down).clamp_min(0.0).to(torch.float32)
+    nonzero = w > 0
+    empty = (~nonzero.any(1)).nonzero().reshape(-1).tolist()
+    if empty:
+        raise ValueError(f"{len(empty)} of {bands} mel bands hold no row of {rows} (the first: band {empty[0]}): fewer bands expected")
+    first = nonzero.to(torch.int8).argmax(1)
+    last = rows - 1 - nonzero.flip(1).to(torch.int8).argmax(1)
+    return w.contiguous(), first.to(torch.int32), (last + 1).to(torch.int32)
+
+
+class LogMel:
+    """The log-mel spectrogram of what a (magnitude, phase-delta) image decodes to, pooled over time: the feature space of
+    evaluate_mel.  Channel 0 is decoded as the codec does ((x + 1) / 2, bark un-scaling; with fewer than 512 rows
+    a row's bark weight is the mean over the STFT bins it stands for), squared to power -- non-negative for any x, so generator
+    outputs outside [-1, 1] are legal --, weighted by mel_filterbank(side_h, bands, f_min, f_max), and log(. + floor) is averaged
+    over side_w / pools columns per pool.  Defaults: side_h // 8 bands, min(32, side_w // 8) pools.
+
+    `floor` = 1e-6 is an unmeasured default: it sets how far below a band's usual power the logarithm still tells values apart (a
+    full-scale band is near 1e-1 .. 1e1 here) and no corpus was used to choose it.
+
+        rows = LogMel(512, 512)(batch)            # (B, 2, 512, 512) float32 cuda -> (B, 64 * 32) float32 cuda
+
+    One launch of csrc/logmel.hip per call; a row depends on its image alone."""
+
+    def __init__(self, side_h: int, side_w: int, bands: Optional[int] = None, pools: Optional[int] = None, f_min: float = 0.0,
+                 f_max: float = 22050.0, floor: float = 1e-6) -> None:
+        if not _is_int(side_h) or not _is_int(side_w) or side_h < 64 or side_w < 1:
+            raise ValueError(f"side_h >= 64 and side_w >= 1 expected, got {side_h} x {side_w}")
+        bands = side_h // 8 if bands is None else bands
+        pools = min(32, max(1, side_w // 8)) if pools is None else pools
+        if not _is_int(pools) or pools < 1 or side_w % pools:
+            raise ValueError(f"a pool count that divides side_w = {side_w} expected, got {pools}")
+        if not 0.0 < float(floor) < float("inf"):
+            raise ValueError(f"a finite floor > 0 expected, got {floor}")
+        self.weight, self.lo, self.hi = mel_filterbank(side_h, bands, f_min, f_max)
+        from .audio.functions import _bark_vector   # the codec's own vector (importing it needs no device)
+        bark = _bark_vector(_MEL_BINS, "cpu").double().view(side_h, _MEL_BINS // side_h).mean(1)
+        self.scale = (1.0 / (2.0 * bark)).to(torch.float32).contiguous()
+        self.side_h, self.side_w, self.bands, self.pools, self.floor = side_h, side_w, bands, pools, float(floor)
+        self.dims = bands * pools
+        self._dev = {}   # device -> (scale, weight) on it
+
+    def __call__(self, x: torch.Tensor) -> torch.Tensor:
+        if x.dim() != 4 or tuple(x.shape[1:]) != (2, self.side_h, self.side_w) or x.shape[0] < 1:
+            raise ValueError(f"a non-empty batch (B, 2, {self.side_h}, {self.side_w}) expected, got {tuple(x.shape)}")
+        ops._chk_typed("LogMel", x)
+        if x.device not in self._dev:
+            self._dev[x.device] = (self.scale.to(x.device), self.weight.to(x.device))
+        scale, weight = self._dev[x.device]
+        return mel_ops.logmel_rows(x, 0, scale, weight, self.lo, self.hi, self.floor, self.pools)
+
+
+def _sym_f64(name: str, mean, cov) -> int:
+    if not all(isinstance(t, torch.Tensor) and t.dtype == torch.float64 and not t.is_cuda for t in (mean, cov)):
+        raise ValueError(f"frechet_distance: {name}: float64 host tensors expected")
+    if mean.dim() != 1 or mean.shape[0] < 1 or tuple(cov.shape) != (mean.shape[0], mean.shape[0]):
+        raise ValueError(f"frechet_distance: {name}: a mean (d,) and a covariance (d, d) expected, got {tuple(mean.shape)} and "
+                         f"{tuple(cov.shape)}")
+    return mean.shape[0]
+
+
+def frechet_distance(mean1: torch.Tensor, cov1: torch.Tensor, mean2: torch.Tensor, cov2: torch.Tensor) -> float:
+    """The Frechet distance between the Gaussians N(mean1, cov1) and N(mean2, cov2) (Dowson & Landau 1982; the formula of FID), in
+    host float64: |mean1 - mean2|^2 + tr cov1 + tr cov2 - 2 sum sqrt(max(l, 0)) over the eigenvalues l of S cov2 S, where S is
+    the positive-semidefinite square root of cov1 from torch.linalg.eigh with negative eigenvalues clamped to 0.  S cov2 S is
+    symmetric and has the eigenvalues of cov1 cov2, so no square root of a non-symmetric matrix is taken; singular covariances
+    (fewer rows than dimensions) are legal.  With cov1 = V diag(a) V^T, the eigenvalues of S cov2 S that are not zero by the rank of
+    cov1 are those of the r x r matrix diag(sqrt a_r) V_r^T cov2 V_r diag(sqrt a_r) over the r eigenpairs with a > d eps max(a) (the
+    numerical rank): that matrix is what is decomposed, so that the d - r known zeros are not computed as rounding noise, whose
+    square root would be 1e-8 of the scale each.  Rounding can leave the result a few 1e-16 (tr cov1 + tr cov2) below 0 for
+    covariances of full rank, and up to 1e-9 of it for singular ones."""
+    d = _sym_f64("the first set", mean1, cov1)
+    if d != _sym_f64("the second set", mean2, cov2):
+        raise ValueError(f"frechet_distance: two sets of one dimension expected, got {mean1.shape[0]} and {mean2.shape[0]}")
+    lam, vec = torch.linalg.eigh((cov1 + cov1.T) / 2)
+    keep = lam > d * torch.finfo(torch.float64).eps * lam.max()          # none for a covariance that is not positive anywhere
+    half = vec[:, keep] * lam[keep].sqrt()
+    inner = half.T @ ((cov2 + cov2.T) / 2) @ half
+    cross = torch.linalg.eigvalsh((inner + inner.T) / 2).clamp_min(0.0).sqrt().sum() if bool(keep.any()) else 0.0
+    delta = mean1 - mean2
+    return float(delta @ delta + torch.trace(cov1) + torch.trace(cov2) - 2.0 * cross)
+
+
+class Frechet:
+    """The Frechet distance between everything fed as real and everything fed as fake, in whatever space the rows are in (LogMel
+    rows in evaluate_mel).  Feeding keeps a device copy; moments() runs mel_ops.moments over all rows of a set at once, so the
+    result is the same bit for bit for any split of the feeds; result() copies the two means and covariances to the host and
+    evaluates frechet_distance there.  At most 4096 numbers per row."""
+
+    def __init__(self) -> None:
+        self.shape = None
+        self._real, self._fake = _RowStore("Frechet"), _RowStore("Frechet")
+        self._moments = None
+
+    def _feed(self, store: _RowStore, what: str, batch: torch.Tensor) -> None:
+        self.shape = store.add(batch, what, self.shape)
+        self._moments = None
+
+    def feed_real(self, batch: torch.Tensor) -> None:
+        self._feed(self._real, "feed_real", batch)
+
+    def feed_fake(self, batch: torch.Tensor) -> None:
+        self._feed(self._fake, "feed_fake", batch)
+
+    def moments(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(mean_real (d,), cov_real (d, d), mean_fake, cov_fake): float64 on the device"""
+        if min(self._real.n, self._fake.n) < 2:
+            raise ValueError(f"{self._real.n} real and {self._fake.n} fake rows fed, at least 2 of each expected")
+        if self._moments is None:
+            self._moments = mel_ops.moments(self._real.rows()) + mel_ops.moments(self._fake.rows())
+        return self._moments
+
+    def result(self) -> float:
+        return frechet_distance(*(t.cpu() for t in self.moments()))
