@@ -888,6 +888,28 @@ int mg_logmel_rows(const float* x, int n, int channels, int c, int h, int w, con
 size_t mg_moments_ws_bytes(int64_t n, int64_t d);
 int mg_moments(const float* rows, int64_t n, int64_t d, double* mean, double* cov, void* ws, size_t ws_bytes, mg_stream_t stream);
 
+/* ---- Kernel Inception Distance (csrc/kid.hip): the kernels behind musicgan_amd/kid_ops.py, metrics.poly_mmd2 and metrics.KID, which
+ * the reference does not have (definition and error bound: DESIGN.md 4.20).
+ * standardise_rows: x (n, d) float32, mean (d,) and sd (d,) float64 -> out (n, d) float32, every element written:
+ *     out[i,j] = (float)(((double)x[i,j] - mean[j]) / sd[j]), and 0 where sd[j] is 0, infinite or NaN.
+ *   One launch, one element per thread; bit-equal to the float64 definition.
+ * polyk_ws_bytes: HOST query, the partial row sums of mg_polyk_rowsums: subsets x ceil(mb / 128) x ma x 8 (0: the shape is refused).
+ * polyk_rowsums: a (na, d) and b (nb, d) float32, d <= 4096; ia (subsets, ma) and ib (subsets, mb) int32 row numbers in DEVICE
+ *   memory, NULL = 0 .. m - 1 for every subset (then m <= n); the rows are gathered while they are staged.  A row number outside its
+ *   operand is clamped into it, so no list can make a read leave a or b.  out (subsets, ma) float64, every element written:
+ *     out[s,i] = sum over j = 0 .. mb - 1 of k(a[ia[s,i]], b[ib[s,j]]),   k(x, y) = (x.y / d + 1)^3,
+ *   without the pairs j = i if skip_diag (which needs ma = mb).  x.y is taken in chunks of 256 components, each a float32 chain from
+ *   zero on v_mfma_f32_16x16x4_f32 (the chunk discipline of mg_nn_sqdist_tiled), the chunks are added in float64 in ascending
+ *   order, and the division, the cube and every sum over pairs are float64 in an order the column positions alone fix: out[s,i] is
+ *   a function of its row of a, the ordered list of b rows of subset s, d and skip_diag (and, with skip_diag, of i) -- not of ma,
+ *   of `subsets`, of the other subsets or of the other rows of a -- and the same bits in every run.  The kernel matrix is never
+ *   stored.  Two launches on `stream` (tiles, then the sum over the column blocks), no atomics, capturable; subsets <= 65535;
+ *   ws at an 8-byte boundary; the part of it that is read was written by the same call. */
+int mg_standardise_rows(const float* x, int64_t n, int64_t d, const double* mean, const double* sd, float* out, mg_stream_t stream);
+size_t mg_polyk_ws_bytes(int64_t subsets, int64_t ma, int64_t mb);
+int mg_polyk_rowsums(const float* a, int64_t na, const float* b, int64_t nb, const int32_t* ia, const int32_t* ib, int64_t subsets,
+                     int64_t ma, int64_t mb, int64_t d, int skip_diag, double* out, void* ws, size_t ws_bytes, mg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

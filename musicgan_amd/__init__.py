@@ -1,8 +1,8 @@
 """musicgan_amd -- the Ipsedo/MusicGAN training hot path on AMD MI355X (gfx950): ProGAN WGAN-GP generator/discriminator step
 and the STFT / magnitude-phase codec, hand-written HIP behind a C ABI (include/musicgan_hip.h), with the reference's Python
 surface (`networks`, `audio`, `train`, `generate`, `create_dataset`, `view_audio`) on top, plus `evaluate` / `metrics`
-(sliced Wasserstein distance of a checkpoint's samples to the data) and `evaluate_mel` (Frechet distance and kNN metrics of log-mel
-spectrograms), which the reference does not have."""
+(sliced Wasserstein distance of a checkpoint's samples to the data) and `evaluate_mel` (Frechet distance, Kernel Inception Distance and kNN
+metrics of log-mel spectrograms), which the reference does not have."""
 
 
 def __getattr__(name):  # lazy: importing the package must not drag in the data/IO stack

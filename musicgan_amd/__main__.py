@@ -10,6 +10,7 @@ _METRICS = ("swd", "msssim", "nn")
 _METRICS_ALL = _METRICS + ("prdc",)
 _METRICS_EVERY = _METRICS_ALL + ("ndb",)
 _MEL_METRICS = ("fd", "nn", "prdc", "ndb")   # evaluate_mel.METRICS
+_MEL_METRICS_ALL = _MEL_METRICS + ("kid",)   # evaluate_mel.METRICS_ALL
 _AUGMENTS = ("translation", "cutout")   # aug_ops.OPS (not imported here: the modes are dispatched lazily)
 
 
@@ -22,8 +23,8 @@ def _metric_list(text: str):
 
 def _mel_metric_list(text: str):
     names = tuple(t.strip() for t in text.split(","))
-    if any(n not in _MEL_METRICS for n in names) or len(set(names)) != len(names):
-        raise argparse.ArgumentTypeError(f"a comma-separated subset of {','.join(_MEL_METRICS)} expected, got {text!r}")
+    if any(n not in _MEL_METRICS_ALL for n in names) or len(set(names)) != len(names):
+        raise argparse.ArgumentTypeError(f"a comma-separated subset of {','.join(_MEL_METRICS_ALL)} expected, got {text!r}")
     return names
 
 
@@ -228,11 +229,13 @@ _FEATURE_MODES = {
         (("--batch-size",), dict(dest="batch_size", type=int, default=16)),
         (("--seed",), dict(type=int, default=0)),
         (("-o", "--output"), dict(type=str, default=None, help="also write the result as JSON to this file")),
-        (("--metrics",), dict(type=_mel_metric_list, default=None, metavar="fd,nn,prdc,ndb",
+        (("--metrics",), dict(type=_mel_metric_list, default=None, metavar="fd,nn,prdc,ndb,kid",
                               help="what to report in the log-mel spectrogram of what the images decode to (default: fd); fd: the "
                                    "Frechet distance between the Gaussians fitted to the generated and to the real rows, with "
                                    "fd_half and fd_real at equal set sizes -- fd_half near fd_real is what a perfect generator "
-                                   "scores; nn, prdc, ndb: as in evaluate, on log-mel rows instead of pixels")),
+                                   "scores; nn, prdc, ndb: as in evaluate, on log-mel rows instead of pixels; kid: the Kernel "
+                                   "Inception Distance on the rows of fd (mean and deviation over 100 subsets of 1000, kid_full on "
+                                   "all images, kid_real for two halves of the data): unbiased, so comparable across set sizes")),
     ], lambda a: (a.gen_dict_state, a.rand_channels, a.input_dataset),
         lambda a: dict(level=a.level, nb_images=a.nb_images, batch_size=a.batch_size, seed=a.seed, output=a.output,
                        **({"metrics": a.metrics} if a.metrics is not None else {}))),

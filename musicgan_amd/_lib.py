@@ -254,6 +254,9 @@ SIGNATURES = {
                                ctypes.c_double, c_int, _P, _P]),
     "mg_moments_ws_bytes": (c_size_t, [c_int64, c_int64]),
     "mg_moments": (c_int, [_P, c_int64, c_int64, _P, _P, _P, c_size_t, _P]),
+    "mg_standardise_rows": (c_int, [_P, c_int64, c_int64, _P, _P, _P, _P]),
+    "mg_polyk_ws_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "mg_polyk_rowsums": (c_int, [_P, c_int64, _P, c_int64, _P, _P, c_int64, c_int64, c_int64, c_int64, c_int, _P, _P, c_size_t, _P]),
 }
 
 _lib = None

@@ -4,7 +4,8 @@ log-mel spectrogram of what each image decodes to (metrics.LogMel, DESIGN.md 4.1
 phase-delta channel, which is close to noise for music, as much as the magnitude, and the magnitude linearly, so that a few loud
 bins decide; the log-mel rows drop the phase, weigh the power by mel band and compress it logarithmically, as every audio evaluation
 does.  "fd": the Frechet distance between the Gaussians fitted to the two sets of rows (the formula of FID; no pretrained network is
-involved).  "nn", "prdc", "ndb": evaluate's own runners on log-mel rows instead of 128 x 128 pixels.
+involved).  "nn", "prdc", "ndb": evaluate's own runners on log-mel rows instead of 128 x 128 pixels.  "kid" (in METRICS_ALL, not in
+METRICS): the Kernel Inception Distance on the rows of "fd", whose expectation does not depend on the set sizes (metrics.KID).
 Single GPU."""
 import json
 import sys
@@ -14,16 +15,23 @@ import torch
 
 _first = f"{__package__}.evaluate" not in sys.modules
 from .evaluate import _FINAL_LEVEL, _Images, _check_sizes, _ndb, _nn, _open, _prdc, evaluate  # noqa: E402
-from .metrics import LogMel, frechet_distance  # noqa: E402
+from .metrics import KID, LogMel, frechet_distance, kid_subsets  # noqa: E402
 from . import mel_ops  # noqa: E402
 
 if _first:   # the import system has just bound the sub-module over the package's lazily exported function `evaluate`: put it back
     setattr(sys.modules[__package__], "evaluate", evaluate)
 
 METRICS = ("fd", "nn", "prdc", "ndb")
+METRICS_ALL = METRICS + ("kid",)
 _MIN_LEVEL = 4        # 64 x 64: LogMel needs 64 rows (8 bands)
 _FD_POOLS = 8         # time pools of the Frechet rows: 64 x 8 = 512 dimensions at level 7, 16 images per dimension at 8192
 _FD_MIN_IMAGES = 4    # two halves of two rows
+_KID_SUBSETS, _KID_SUBSET_SIZE = 100, 1000   # the protocol of Binkowski et al. 2018
+_KID_MIN_IMAGES = 4   # two halves of two rows
+# kid draws its generated images in batches of this many, whatever batch_size is: the generator's kernels are chosen by the batch
+# size, so the images differ in their last float32 bits from one batching to another, and a number that is there to be compared
+# across runs must not move with --batch-size.  16 is every driver's default: a default run draws exactly evaluate's images.
+_KID_FAKE_BATCH = 16
 
 
 class _MelImages(_Images):
@@ -69,14 +77,44 @@ def _fd(images: _Images, nb_images: int, perm, seed: int) -> Dict[str, float]:
     return result
 
 
+def _kid(images: _Images, nb_images: int, perm, seed: int) -> Dict[str, float]:
+    half, side = nb_images // 2, images.side
+    logmel = LogMel(side, side, pools=min(_FD_POOLS, side // 8))      # the rows of fd
+    kid = KID(_KID_SUBSETS, _KID_SUBSET_SIZE, seed)
+    for lo, hi in images.batches(nb_images):
+        kid.feed_real(logmel(images.real(range(lo, hi))))
+    for lo in range(0, nb_images, _KID_FAKE_BATCH):
+        kid.feed_fake(logmel(images.fake(slice(lo, min(lo + _KID_FAKE_BATCH, nb_images)))))
+    result = kid.result()
+    # the two random halves of the real set that fd_real compares, standardised by the whole real set's moments like everything else
+    real = kid.standardised()[0]
+    first = real[torch.tensor(perm[:half], device=real.device)].contiguous()
+    second = real[torch.tensor(perm[half:2 * half], device=real.device)].contiguous()
+    result["kid_real"], result["kid_real_std"] = kid_subsets(first, second, _KID_SUBSETS, _KID_SUBSET_SIZE, seed)
+    space = f"in log-mel space ({logmel.bands} bands x {logmel.pools} pools, standardised by the real images' moments)"
+    m, m_real = min(_KID_SUBSET_SIZE, nb_images), min(_KID_SUBSET_SIZE, half)
+    count = lambda m, n: "1 subset" if m == n else f"{_KID_SUBSETS} subsets"   # noqa: E731
+    print(f"KID [     kid] = {result['kid']:.6f} +- {result['kid_std']:.6f} {space}, {count(m, nb_images)} of {m} real against "
+          f"{m} generated images")
+    print(f"KID [kid_full] = {result['kid_full']:.6f} {space}, {nb_images} real against {nb_images} generated images")
+    print(f"KID [kid_real] = {result['kid_real']:.6f} +- {result['kid_real_std']:.6f} {space}, "
+          f"{count(m_real, half)} of {m_real} real against {m_real} real images")
+    print("KID: the unbiased estimate of the squared MMD under k(x, y) = (x.y / d + 1)^3: its expectation does not depend on the "
+          "set sizes and is 0 for two samples of one distribution, so it can be negative; kid_real (one random half of the data "
+          "against the other) shows how far from 0 chance alone puts it")
+    return result
+
+
 # metric: its runner; nn, prdc and ndb are evaluate's, their least image counts with them
-_RUNNERS = {"fd": _fd, "nn": _nn, "prdc": _prdc, "ndb": _ndb}
-assert tuple(_RUNNERS) == METRICS
+_RUNNERS = {"fd": _fd, "nn": _nn, "prdc": _prdc, "ndb": _ndb, "kid": _kid}
+assert tuple(_RUNNERS) == METRICS_ALL
 
 
 def _check(metrics: Sequence[str], nb_images: int) -> None:
     if "fd" in metrics and nb_images < _FD_MIN_IMAGES:
         raise ValueError(f"fd needs at least {_FD_MIN_IMAGES} images (two halves of two), got {nb_images}")
+    if "kid" in metrics and nb_images < _KID_MIN_IMAGES:
+        raise ValueError(f"kid needs at least {_KID_MIN_IMAGES} images (two halves of two), got {nb_images}")
     _check_sizes(metrics, nb_images)
 
 
@@ -85,7 +123,7 @@ def evaluate_mel(gen_dict_state: str, rand_channels: int, input_dataset: str, me
                  output: Optional[str] = None) -> Dict[str, float]:
     """`level`: the growth level the checkpoint was saved at, 4 (64 x 64) .. 7 (fully grown, 512 x 512); real samples are brought to
     that level's side by the training loop's own input transform and are not reduced further.  `metrics`: a subset of ("fd", "nn",
-    "prdc", "ndb"), run in that order.  The images, the one draw of latents and the seeded order of the dataset are evaluate's for
+    "prdc", "ndb", "kid"), run in that order.  The images, the one draw of latents and the seeded order of the dataset are evaluate's for
     the same arguments.  Returns the keys of the metrics asked for and writes them as JSON to `output`.
 
     "fd": rows are LogMel(side, side, pools=min(8, side // 8)) -- side // 8 mel bands x 8 time pools, 512 dimensions at level 7.
@@ -95,19 +133,29 @@ def evaluate_mel(gen_dict_state: str, rand_channels: int, input_dataset: str, me
     `fd_real` have the same set sizes, and `fd_half` near `fd_real` is what a perfect generator scores.  Needs nb_images >= 4.
 
     "nn", "prdc", "ndb": evaluate's runners with the same counts, queries and keys, on LogMel(side, side) rows (side // 8 bands x
-    min(32, side // 8) pools) instead of pixels at 128 x 128; their lines name the space."""
+    min(32, side // 8) pools) instead of pixels at 128 x 128; their lines name the space.
+
+    "kid" (not in the default tuple METRICS; METRICS_ALL has it): the rows of "fd", standardised column by column with the real
+    set's float64 mean and standard deviation.  `kid` / `kid_std` = the mean and population standard deviation, over 100 random
+    subsets of min(1000, nb_images) images of each set, of the unbiased estimate of the squared maximum mean discrepancy under
+    k(x, y) = (x.y / d + 1)^3 (Binkowski et al. 2018; one subset and a deviation of 0.0 if that is all images); `kid_full` = the
+    estimate on the whole sets; `kid_real` / `kid_real_std` = the same protocol for the two random halves of the real set that
+    `fd_real` compares, whose expectation is 0.  Unlike `fd`, the estimate's expectation does not depend on the set sizes, so runs
+    at different nb_images can be compared; it can be negative.  The generated images of "kid" are drawn in batches of 16 whatever
+    `batch_size` is (the real ones in batches of `batch_size`; a real row does not depend on its batch), so none of the five numbers
+    depends on `batch_size`; at the default batch size they are the images of the other metrics.  Needs nb_images >= 4."""
     if not _MIN_LEVEL <= level <= _FINAL_LEVEL:
         raise ValueError(f"level must be in {_MIN_LEVEL} .. {_FINAL_LEVEL} (log-mel rows need at least 64 image rows), got {level}")
     if nb_images < 1 or batch_size < 1:
         raise ValueError("nb_images and batch_size must be positive")
     metrics = tuple(metrics)
-    if not metrics or any(m not in METRICS for m in metrics) or len(set(metrics)) != len(metrics):
-        raise ValueError(f"metrics: a non-empty subset of {METRICS} expected, got {metrics}")
+    if not metrics or any(m not in METRICS_ALL for m in metrics) or len(set(metrics)) != len(metrics):
+        raise ValueError(f"metrics: a non-empty subset of {METRICS_ALL} expected, got {metrics}")
     _check(metrics, nb_images)   # before any work ...
     images, nb_images, perm = _open(_MelImages, lambda n: _check(metrics, n), gen_dict_state, rand_channels, input_dataset, level,
                                     nb_images, batch_size, seed)
     result = {}
-    for name in METRICS:
+    for name in METRICS_ALL:
         if name in metrics:
             result.update(_RUNNERS[name](images, nb_images, perm, seed))
     if output is not None:

@@ -59,7 +59,19 @@ csrc/logmel.hip and csrc/moments.hip through musicgan_amd/mel_ops.py.
     fd = Frechet()
     for batch in real:  fd.feed_real(rows(batch)) # any (B, ...) float32 cuda batch, any split
     for batch in fake:  fd.feed_fake(rows(batch))
-    fd.result()                                   # float; fd.moments(): the float64 means and covariances, on the device"""
+    fd.result()                                   # float; fd.moments(): the float64 means and covariances, on the device
+
+(7) The Kernel Inception Distance in the same rows (Binkowski et al., "Demystifying MMD GANs", ICLR 2018): the unbiased estimate of
+the squared maximum mean discrepancy under k(x, y) = (x.y / d + 1)^3, as mean and standard deviation over random subsets.  Its
+expectation does not depend on the set sizes, which the Frechet distance's does.  Definition and error bound: DESIGN.md 4.20;
+kernels: csrc/kid.hip through musicgan_amd/kid_ops.py -- no kernel matrix is stored.
+
+    kid = KID(subsets=100, subset_size=1000)
+    for batch in real:  kid.feed_real(rows(batch))  # any (B, ...) float32 cuda batch, any split, any interleaving
+    for batch in fake:  kid.feed_fake(rows(batch))
+    kid.result()                                  # {"kid": .., "kid_std": .., "kid_full": ..}; rows standardised by the real moments
+    kid.per_sample()                              # (n_fake,) float64 cuda: the witness function at every generated row
+    poly_mmd2(x, y)                               # the estimate for two row tensors as they are"""
 from __future__ import annotations
 
 import math
@@ -68,7 +80,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
-from . import km_ops, mel_ops, nn_ops, ops, ssim_ops
+from . import kid_ops, km_ops, mel_ops, nn_ops, ops, ssim_ops
 
 
 def pyramid_sides(side_h: int, side_w: int, min_side: int = 16) -> List[Tuple[int, int]]:
@@ -892,3 +904,133 @@ class Frechet:
 
     def result(self) -> float:
         return frechet_distance(*(t.cpu() for t in self.moments()))
+
+
+# ------------------------------------------------------------------ kernel distance (KID)
+def _kid_rows(x, what: str) -> torch.Tensor:
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] < 2 or not 1 <= x.shape[1] <= kid_ops.MAX_D:
+        raise ValueError(f"{what}: at least 2 rows (n, d) of 1 .. {kid_ops.MAX_D} numbers expected, got "
+                         f"{tuple(x.shape) if isinstance(x, torch.Tensor) else x!r}")
+    return x
+
+
+def _mmd2_sums(x: torch.Tensor, y: torch.Tensor, ix: Optional[torch.Tensor] = None, iy: Optional[torch.Tensor] = None):
+    """three fused launches: the row sums of k over x x x and y x y without their diagonals and over y x x, per subset.  Returns
+    ((subsets, 3) float64: their totals per subset, the y x y row sums, the y x x row sums), all on the device."""
+    xx = kid_ops.polyk_rowsums(x, x, ix, ix, skip_diag=True)
+    yy = kid_ops.polyk_rowsums(y, y, iy, iy, skip_diag=True)
+    yx = kid_ops.polyk_rowsums(y, x, iy, ix)
+    return torch.stack([xx.sum(1), yy.sum(1), yx.sum(1)], 1), yy, yx
+
+
+def _mmd2(totals: Sequence[float], m: int, n: int) -> float:
+    """the unbiased estimate from the three totals of a subset of m and n rows, in host float64"""
+    sxx, syy, syx = totals
+    return sxx / (m * (m - 1)) + syy / (n * (n - 1)) - 2.0 * syx / (m * n)
+
+
+def poly_mmd2(x: torch.Tensor, y: torch.Tensor) -> float:
+    """The unbiased estimate of the squared maximum mean discrepancy between the rows x (m, d) and y (n, d) (float32 cuda, m, n
+    >= 2, d <= 4096) under k(a, b) = (a.b / d + 1)^3:
+        sum_{i != j} k(x_i, x_j) / (m (m - 1)) + sum_{i != j} k(y_i, y_j) / (n (n - 1)) - 2 sum_{i, j} k(y_i, x_j) / (m n).
+    It can be negative.  The rows are taken as they are (KID standardises them first).  Three kid_ops.polyk_rowsums launches, the
+    float64 row sums are added on the device and read back once; the same bits in every run."""
+    x, y = _kid_rows(x, "poly_mmd2"), _kid_rows(y, "poly_mmd2")
+    if x.shape[1] != y.shape[1]:
+        raise ValueError(f"poly_mmd2: rows of one length expected, got {x.shape[1]} and {y.shape[1]}")
+    totals, _, _ = _mmd2_sums(x, y)
+    return _mmd2(totals[0].tolist(), x.shape[0], y.shape[0])
+
+
+def _kid_counts(subsets, subset_size, seed) -> None:
+    for name, v, least, most in (("subsets", subsets, 1, kid_ops.MAX_SUBSETS), ("subset_size", subset_size, 2, kid_ops.MAX_ROWS)):
+        if isinstance(v, bool) or not isinstance(v, int) or not least <= v <= most:
+            raise ValueError(f"{name} in {least} .. {most} expected, got {v!r}")
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise ValueError(f"an integer seed expected, got {seed!r}")
+
+
+def kid_subsets(x: torch.Tensor, y: torch.Tensor, subsets: int = 100, subset_size: int = 1000, seed: int = 0) -> Tuple[float, float]:
+    """(mean, population standard deviation) of poly_mmd2 over `subsets` random subsets of m = min(subset_size, rows of x, rows of
+    y) rows of each set (the protocol of Binkowski et al.).  Subset s takes the first m entries of a permutation of each set from
+    one CPU generator seeded with `seed`: x's permutation of subset 0, y's of subset 0, x's of subset 1, ...  If m is the size of
+    both sets the one subset there is is run, and the deviation is 0.0.  All subsets go through three batched launches."""
+    x, y = _kid_rows(x, "kid_subsets"), _kid_rows(y, "kid_subsets")
+    _kid_counts(subsets, subset_size, seed)
+    m = min(subset_size, x.shape[0], y.shape[0])
+    if m == x.shape[0] == y.shape[0]:
+        return poly_mmd2(x, y), 0.0
+    gen = torch.Generator().manual_seed(seed)
+    ix, iy = [], []
+    for _ in range(subsets):
+        ix.append(torch.randperm(x.shape[0], generator=gen)[:m])
+        iy.append(torch.randperm(y.shape[0], generator=gen)[:m])
+    ix, iy = (torch.stack(lists).to(torch.int32).to(x.device) for lists in (ix, iy))
+    totals, _, _ = _mmd2_sums(x, y, ix, iy)
+    values = [_mmd2(row, m, m) for row in totals.tolist()]
+    mean = math.fsum(values) / subsets
+    return mean, math.sqrt(math.fsum((v - mean) ** 2 for v in values) / subsets)
+
+
+class KID:
+    """The Kernel Inception Distance between everything fed as real and everything fed as fake, in whatever space the rows are in
+    (LogMel rows in evaluate_mel).  Feeding keeps a device copy.  result() standardises both sets by the real rows' float64 mean
+    and standard deviation (mel_ops.moments; a column without variance becomes 0) -- without that the polynomial kernel sees
+    little but the common offset of log-mel rows -- and returns `kid` / `kid_std`, the mean and population standard deviation of
+    the unbiased estimate over `subsets` random subsets of min(subset_size, n_real, n_fake) rows (kid_subsets), and `kid_full`,
+    the estimate on the whole sets.  per_sample(): the witness function at every generated row.  Every sum is float64 in a fixed
+    order and the rows of a set are concatenated before anything is launched: every output is the same bit for bit for any split
+    and interleaving of the feeds.  At most 4096 numbers per row."""
+
+    KEYS = ("kid", "kid_std", "kid_full")
+
+    def __init__(self, subsets: int = 100, subset_size: int = 1000, seed: int = 0) -> None:
+        _kid_counts(subsets, subset_size, seed)
+        self.subsets, self.subset_size, self.seed, self.shape = subsets, subset_size, seed, None
+        self._real, self._fake = _RowStore("KID"), _RowStore("KID")
+        self._rows = self._full = None
+
+    def _feed(self, store: _RowStore, what: str, batch: torch.Tensor) -> None:
+        self.shape = store.add(batch, what, self.shape)
+        self._rows = self._full = None
+
+    def feed_real(self, batch: torch.Tensor) -> None:
+        self._feed(self._real, "feed_real", batch)
+
+    def feed_fake(self, batch: torch.Tensor) -> None:
+        self._feed(self._fake, "feed_fake", batch)
+
+    def standardised(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(real (n_real, d), fake (n_fake, d)) float32 on the device: the rows the kernel sees"""
+        if min(self._real.n, self._fake.n) < 2:
+            raise ValueError(f"{self._real.n} real and {self._fake.n} fake rows fed, at least 2 of each expected")
+        if self._rows is None:
+            real, fake = self._real.rows(), self._fake.rows()
+            if real.shape[1] > kid_ops.MAX_D:
+                raise ValueError(f"KID: at most {kid_ops.MAX_D} numbers per row, got {real.shape[1]}")
+            mean, cov = mel_ops.moments(real)
+            sd = cov.diagonal().sqrt().contiguous()
+            self._rows = kid_ops.standardise_rows(real, mean, sd), kid_ops.standardise_rows(fake, mean, sd)
+        return self._rows
+
+    def _whole(self):
+        if self._full is None:
+            real, fake = self.standardised()
+            totals, yy, yx = _mmd2_sums(real, fake)
+            self._full = _mmd2(totals[0].tolist(), real.shape[0], fake.shape[0]), yy[0], yx[0]
+        return self._full
+
+    def per_sample(self) -> torch.Tensor:
+        """(n_fake,) float64 on the device: for every generated row y_i the witness function of the two whole sets,
+        mean_j k(y_i, x_j) - mean_{j != i} k(y_i, y_j): positive where the data is denser around y_i than the samples are.  The
+        smallest values name the samples least like the data."""
+        _, yy, yx = self._whole()
+        return yx / self._real.n - yy / (self._fake.n - 1)
+
+    def result(self) -> Dict[str, float]:
+        real, fake = self.standardised()
+        full = self._whole()[0]
+        if min(self.subset_size, real.shape[0], fake.shape[0]) == real.shape[0] == fake.shape[0]:
+            return {"kid": full, "kid_std": 0.0, "kid_full": full}    # the one subset there is: the whole sets
+        kid, std = kid_subsets(real, fake, self.subsets, self.subset_size, self.seed)
+        return {"kid": kid, "kid_std": std, "kid_full": full}
