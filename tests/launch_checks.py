@@ -53,7 +53,7 @@ def step_census(monkeypatch, level, batch, fused_d_step=True):
     og = FusedAdam(gen.parameters(), lr=1e-3, betas=(0.0, 0.9))
     od = FusedAdam(disc.parameters(), lr=1e-3, betas=(0.0, 0.9))
     st = ProGANStepper(gen, disc, og, od, 32, fused_d_step=fused_d_step)
-    side = bench.LEVEL_SIDE[level]
+    side = 4 << level  # bench.LEVEL_SIDE where that has the level (test_launch_checks_cpu.py); levels 0-2 are below its table
     rng = torch.Generator(device=DEV).manual_seed(1234)
     x_real = torch.rand(batch, 2, side, side, device=DEV, generator=rng) * 2 - 1
     z = torch.randn(batch, 32, 2, 2, device=DEV, generator=rng)
@@ -459,6 +459,38 @@ def _check_ends(name, a, g):
         _report("blend_up_bwd b sums", gy, a["b"] * 4.0 * F.avg_pool2d(h(kw["g"]), 2), 2e-6)
 
 
+# ------------------------------------------------------------------ the lone 1x1 convs of level 0, where neither end has a partner to
+# fuse with: the critic's stem (2 -> C, LeakyReLU), its tangent form (bias-free, times the LeakyReLU derivative of the saved
+# activation, written over it), its data gradient (C -> 2 with w^T) and the generator's head (C -> 2, tanh)
+def _check_conv1x1(name, a, g):
+    ops = _ops()
+    known = {"x", "w", "bias", "cout", "lrelu", "tanh", "mask_aux", "transposed", "out"}
+    assert set(a) <= known and sum(bool(a.get(k)) for k in ("lrelu", "tanh", "transposed")) + (a.get("mask_aux") is not None) == 1, \
+        f"no headline-shape check for conv1x1 with {sorted(set(a) - {'x', 'w', 'bias', 'cout'})}"
+    kw = _inputs(g, a, skip=("out",))
+    kw["w"] = kw["w"] / math.sqrt(a["x"][1])  # pre-activations of order 1: tanh neither saturated nor linear
+    mask = kw.get("mask_aux")
+    mask0 = mask.clone() if mask is not None else None
+    if a.get("out") is not None:
+        # the tangent pass writes over the activation it reads its mask from (disc_step_fused); any other `out` is written in full
+        kw["out"] = mask if mask is not None and tuple(mask.shape) == a["out"] else torch.full(a["out"], float("nan"), device=DEV)
+    got = ops.conv1x1(**kw)
+    assert a.get("out") is None or got is kw["out"]
+    assert tuple(got.shape) == (a["x"][0], a["cout"]) + tuple(a["x"][2:])
+    x, w64 = kw["x"], _host(kw["w"])
+    b64 = _host(kw["bias"]) if kw.get("bias") is not None else None
+    # bounds of test_conv1x1_all_modes: "stem" and "stem tangent" 2e-6, "head" and "stem dgrad" 3e-6
+    if a.get("transposed"):
+        assert b64 is None
+        _check("conv1x1 transposed", got, lambda i0, i1: F.conv_transpose2d(_host(x, i0, i1), w64), 3e-6)
+    elif a.get("tanh"):
+        _check("conv1x1 tanh", got, lambda i0, i1: torch.tanh(F.conv2d(_host(x, i0, i1), w64, b64)), 3e-6)
+    elif a.get("lrelu"):
+        _check("conv1x1 lrelu", got, lambda i0, i1: F.leaky_relu(F.conv2d(_host(x, i0, i1), w64, b64), SLOPE), 2e-6)
+    else:
+        _check("conv1x1 masked", got, lambda i0, i1: F.conv2d(_host(x, i0, i1), w64, b64) * _slope(_host(mask0, i0, i1)), 2e-6)
+
+
 # ------------------------------------------------------------------ the kernels without an off switch (on both sides of
 # test_full_size_step_is_algorithm_independent): PixelNorm, up-sampling / pooling, LeakyReLU, classifier, penalty, 1x1 weight gradient
 def _check_elementwise(name, a, g):
@@ -560,7 +592,7 @@ def _check_elementwise(name, a, g):
 CHECKS = {"conv3x3": _check_conv, "conv3x3_small": _check_conv, "winoups3x3": _check_upconv, "winoups3x3_head": _check_upconv,
           "upconv3x3": _check_upconv, "winoups3x3_dgrad": _check_winoups_dgrad, "winoups3x3_dgrad_pn": _check_winoups_dgrad,
           "stem_pair": _check_ends, "stem_pair_gx": _check_ends, "head_pair_from_mp": _check_ends, "gen_head_bwd": _check_ends,
-          "blend_up_bwd": _check_ends, "head_pair": _check_ends}
+          "blend_up_bwd": _check_ends, "head_pair": _check_ends, "conv1x1": _check_conv1x1}
 
 
 def check_launch(line, hook=None):

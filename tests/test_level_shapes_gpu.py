@@ -8,6 +8,19 @@ small-map kernel with its un-pooling and block-sum epilogues, weight-gradient sw
 16- and 32-channel layers at 256 x 256 and 512 x 512.  No list holds an `upconv3x3_dgrad` launch; the one `upconv3x3` (level 4) has
 64 output channels.
 
+Levels 0, 1 and 2 (2x4x4, 8x8, 16x16: the first three stages of a training run) follow, at batch 6 (the batch the reference and
+train.py train with: 18 images through the critic) and batch 64 (192 images, the benchmark's batch), appended so that the ids and
+the de-duplication order of the configurations above stay as they were.  What their lists add: level 0 has no fade-in, so both
+ends are lone `conv1x1` launches -- the generator's head with `tanh` (into the step's `out` buffer, or a fresh tensor), the critic's
+stem with `lrelu`, its tangent form written over the activation it takes its mask from, and its data gradient (`transposed`) --
+which no other level launches and `launch_checks._check_conv1x1` restates; there is no `stem_pair`, `head_pair`, blend or
+`conv3x3_fade` there, and the only generator head gradient is a `gen_head_bwd` without `g_in`.  Levels 1 and 2 take the fade-in
+ends at 8x8 and 16x16 (`head_pair`, `stem_pair` without a tile mask and in its tangent form, `stem_pair_gx`, `blend_up_bwd`,
+`axpby` / `blend_lrelu_bwd` where the blend is not fused), the small-map kernel on nearly every 3x3 layer above 1x1 at batch 6
+(all but the critic's 18 images at 16x16) and the Winograd kernels on the 8x8 and 16x16 maps at batch 64, with tile masks (level 2
+is the lowest level that launches `conv3x3_fade`, in all three modes, at 8x8), and weight-gradient sweeps of 4 + 2 up to 8 + 6
+layers on maps of 1x1 to 16x16.  The multi-layer `SmallNet` chains are opt-in (MG_SMALLNET=1) and appear in no list.
+
 `census_level<L>_batch<B>.txt` next to this file is the routing census (tests/routing_census.py) of one critic + one generator
 update of that configuration, committed: under `[launches]` its distinct launches, under `[critic sweep]` / `[generator sweep]`
 the deferred weight gradients of each flush in call order, one `routing_census.spec` line per row.
@@ -30,7 +43,7 @@ from test_headline_shapes_gpu import LAUNCHES as HEADLINE
 
 pytestmark = pytest.mark.gpu
 
-CONFIGS = [(3, 8), (4, 32), (6, 6), (7, 6)]
+CONFIGS = [(3, 8), (4, 32), (6, 6), (7, 6), (0, 6), (1, 6), (2, 6), (0, 64), (1, 64), (2, 64)]
 SECTIONS = ("launches", "critic sweep", "generator sweep")
 
 
@@ -121,11 +134,14 @@ def _kind(line):
         return f"{name}-{kind}"
     if name == "conv3x3_fade":
         return f"{name}-mode{a['mode']}"
+    if name == "conv1x1":  # the comparison of launch_checks._check_conv1x1 it takes
+        kind = "transposed" if a.get("transposed") else "tanh" if a.get("tanh") else "lrelu" if a.get("lrelu") else "masked"
+        return f"{name}-{kind}"
     return name
 
 
 def _first_of_each_kind():
-    """kind -> the first line of that kind, at the smallest configuration that launches it ((3, 8) for nearly all)."""
+    """kind -> the first line of that kind, in the order of CONFIGS ((3, 8) for nearly all; (0, 6) for the lone 1x1 convs)."""
     out = {}
     for cfg in CONFIGS:
         for line in CENSUS[cfg]["launches"]:

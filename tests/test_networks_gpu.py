@@ -269,7 +269,7 @@ def _oracle_full_step(level, batch):
         for _ in range(level):
             gs.next_layer()
             ds.next_layer()
-        side = bench.LEVEL_SIDE[level]
+        side = 4 << level  # bench.LEVEL_SIDE where that has the level (test_launch_checks_cpu.py); levels 0-2 are below its table
         rng = torch.Generator().manual_seed(1234)
         x_real = torch.rand(batch, 2, side, side, generator=rng) * 2 - 1
         z = torch.randn(batch, 32, 2, 2, generator=rng)
@@ -283,7 +283,8 @@ def _oracle_full_step(level, batch):
     return _ORACLE_CACHE[key]
 
 
-@pytest.mark.parametrize("level,batch", [(5, 2), (4, 32), (6, 1), (7, 1), (5, 16), (3, 8), (6, 6), (5, 64)])
+@pytest.mark.parametrize("level,batch", [(5, 2), (4, 32), (6, 1), (7, 1), (5, 16), (3, 8), (6, 6), (5, 64),
+                                         (0, 6), (1, 6), (2, 6), (2, 64)])
 def test_full_size_step_against_fp64_oracle(level, batch, conv_mode):
     """BASELINE.json's shapes against the ORACLE (not against another HIP path): the headline level 5 (2x128x128; batch 2 -- the
     critic then runs on 6 images, every kernel on the tiling it uses at batch 64 -- batch 16: 48 images through the critic, and
@@ -334,7 +335,7 @@ def test_full_size_step_against_fp64_oracle(level, batch, conv_mode):
     print(f"level {level} batch {batch} [{conv_mode}]: worst gradient error / budget {worst:.2f}")
 
 
-@pytest.mark.parametrize("case", ["l1_rc8_fade", "l3_rc32_fade", "l2_direct", "l2_rc16_gpnorm1", "l2_rc16_gpnorm3"])
+@pytest.mark.parametrize("case", ["l1_rc8_fade", "l3_rc32_fade", "l2_direct", "l2_rc16_gpnorm1", "l2_rc16_gpnorm3", "l0_rc8"])
 def test_fused_d_step_equals_module_path(case, conv_mode):
     """ProGANStepper's fused critic step (one batched pass over [real|fake|interpolated], in-place tangent pass, one wgrad
     launch per layer) produces the gradients of the reference-shaped module path and of the fp64 oracle."""

@@ -235,7 +235,8 @@ def test_pixelnorm_bwd_alone(shape):
 
 
 # ------------------------------------------------------------------ (c) whole updates at every level
-STEPS = [(3, 8, 0.5), (4, 8, 0.5), (5, 6, 0.5), (5, 6, 1.0), (5, 6, 0.0), (6, 2, 0.5), (7, 1, 0.5)]
+STEPS = [(3, 8, 0.5), (4, 8, 0.5), (5, 6, 0.5), (5, 6, 1.0), (5, 6, 0.0), (6, 2, 0.5), (7, 1, 0.5),
+         (0, 6, 0.5), (1, 6, 0.5), (2, 6, 0.5), (2, 64, 0.5)]  # level 0 has no fade-in: alpha is unused there
 
 
 @pytest.mark.parametrize("level, batch, alpha", STEPS)
@@ -253,7 +254,7 @@ def test_whole_update(level, batch, alpha):
         og = FusedAdam(gen.parameters(), lr=1e-3, betas=(0.0, 0.9))
         od = FusedAdam(disc.parameters(), lr=1e-3, betas=(0.0, 0.9))
         st = ProGANStepper(gen, disc, og, od, 32)
-        side = bench.LEVEL_SIDE[level]
+        side = 4 << level  # bench.LEVEL_SIDE where that has the level (test_launch_checks_cpu.py); levels 0-2 are below its table
         rng = torch.Generator(device=DEV).manual_seed(1234)
         x_real = torch.rand(batch, 2, side, side, device=DEV, generator=rng) * 2 - 1
         z = torch.randn(batch, 32, 2, 2, device=DEV, generator=rng)
