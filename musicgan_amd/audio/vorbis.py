@@ -705,14 +705,7 @@ def _pack_setup(s: Setup):
     fpos += 256
     tw = []
     for n in s.blocksize:
-        M = n // 2
-        t = np.arange(M // 2)
-        pre = np.exp(-1j * np.pi * (t + 0.25) / M)
-        post = np.exp(-1j * np.pi * t / M)
-        fft = np.exp(-2j * np.pi * np.arange(max(M // 4, 1)) / (M // 2))
-        slope = window_slope(n // 2)
-        block = np.concatenate([np.stack([pre.real, pre.imag], 1).reshape(-1), np.stack([post.real, post.imag], 1).reshape(-1),
-                                np.stack([fft.real, fft.imag], 1).reshape(-1), slope]).astype(np.float32)
+        block = np.concatenate([dct4_tables(n // 2), window_slope(n // 2)]).astype(np.float32)
         tw.append(fpos)
         floats.append(block)
         fpos += len(block)
@@ -720,6 +713,16 @@ def _pack_setup(s: Setup):
     allints = np.concatenate([ints, recs] + tabs)
     assert allints.min() >= -(1 << 31) and allints.max() < (1 << 31)
     return allints.astype(np.int32), np.concatenate(floats).astype(np.float32)
+
+
+def dct4_tables(M: int) -> np.ndarray:
+    """the tables of csrc/fft_radix2.h's dct4_lds for M coefficients, as (re, im) pairs one after the other (float64):
+    pre[t] = e^{-i pi (t + 1/4) / M} and post[t] = e^{-i pi t / M}, t < M / 2; fft[j] = e^{-2 pi i j / (M / 2)}, j < M / 4"""
+    t = np.arange(M // 2)
+    pre = np.exp(-1j * np.pi * (t + 0.25) / M)
+    post = np.exp(-1j * np.pi * t / M)
+    fft = np.exp(-2j * np.pi * np.arange(max(M // 4, 1)) / (M // 2))
+    return np.concatenate([np.stack([z.real, z.imag], 1).reshape(-1) for z in (pre, post, fft)])
 
 
 def inverse_db_table() -> np.ndarray:

@@ -273,13 +273,7 @@ class _Setup:
         ints[TI_BIN:TI_BIN + N2] = np.searchsorted(xs, np.arange(N2), side="right") - 1
         ints[TI_CODES:TI_CODES + len(codes)] = codes
         ints[TI_CODES + len(codes):] = lens
-        M, H = N2, N2 // 2
-        t = np.arange(H)
-        pre = np.exp(-1j * np.pi * (t + 0.25) / M)
-        post = np.exp(-1j * np.pi * t / M)
-        fft = np.exp(-2j * np.pi * np.arange(H // 2) / H)
-        cplx = lambda z: np.stack([z.real, z.imag], 1).reshape(-1)  # noqa: E731
-        floats = np.concatenate([V.window_slope(N2), cplx(pre), cplx(post), cplx(fft), V.inverse_db_table()])
+        floats = np.concatenate([V.window_slope(N2), V.dct4_tables(N2), V.inverse_db_table()])
         assert len(floats) == TF_SIZE
         return ints.astype(np.int32), floats.astype(np.float32)
 

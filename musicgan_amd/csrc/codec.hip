@@ -7,6 +7,7 @@
 // scan over the whole chip (codec_row_pass); the inverse's cumulative phase (functions.py:117-118) is a Python loop of float32
 // adds in the reference, so it runs SEQUENTIALLY per frequency row in fp32 here too (inv_phase_cumsum: one lane per row walks
 // time through LDS tiles).  Everything else is embarrassingly parallel and HBM-bound (8 B in + 8 B out per bin).
+#include "fft_radix2.h"
 #include "mg_common.h"
 #include "sleef_f32.h"
 
@@ -441,20 +442,7 @@ __global__ void __launch_bounds__(256) inv_frames(const float2* __restrict__ Z, 
     buf[rev] = v;
   }
   __syncthreads();
-  for (int len = 2; len <= NFFT; len <<= 1) {
-    const int half = len >> 1;
-    for (int i = tid; i < NFFT / 2; i += 256) {
-      const int grp = i / half, pos = i - grp * half;
-      const int a = grp * len + pos, b = a + half;
-      float s, c;
-      sincospif(2.0f * (float)pos / (float)len, &s, &c);  // inverse transform: e^{+2 pi i pos/len}
-      const float2 x = buf[a], y = buf[b];
-      const float2 wy = make_float2(y.x * c - y.y * s, y.x * s + y.y * c);
-      buf[a] = make_float2(x.x + wy.x, x.y + wy.y);
-      buf[b] = make_float2(x.x - wy.x, x.y - wy.y);
-    }
-    __syncthreads();
-  }
+  fft_radix2_lds(buf, 10, tid, 256, TwInverse{});  // lg NFFT stages of the inverse transform
   const float norm = 19.595917942265423f / (float)NFFT;  // sqrt(384) / N
   for (int i = tid; i < NFFT; i += 256) {
     float s, c;

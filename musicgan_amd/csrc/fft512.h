@@ -1,9 +1,22 @@
-// The 512-point complex FFT of one wave, shared by the forward STFT (stft.hip) and its inverse (griffinlim.hip): complex
-// arithmetic on register pairs, the 8-point butterfly, and the three radix-8 Stockham passes with their two LDS exchanges.
+// The 1024 / 256 transform shared by the forward STFT (stft.hip) and its inverse (griffinlim.hip): the tile constants, the
+// twiddle tables, complex arithmetic on register pairs, the 8-point butterfly, and the 512-point complex FFT of one wave
+// (three radix-8 Stockham passes with their two LDS exchanges).
 #pragma once
 #include "mg_common.h"
 
 namespace {
+
+constexpr int NFFT = 1024, HOP = 256, NB = 512;  // NB = complex points = output bins
+constexpr int NWAVE = 8;                          // waves per workgroup
+constexpr int FPW = 2;                            // frames per wave and tile
+// per-frame LDS column (float2 units).  XSTR = 2 (mod 32): in the transposed read-out the 16 frames of one bin row land on the
+// even 8-byte slots of the 256-byte bank row and the next bin row's on the odd ones, so a 32-lane ds_read_b64 group is conflict-free
+constexpr int XSTR = NB + 2;
+// twiddle tables, each laid out in the order its pass reads it (lane-contiguous or broadcast: no bank conflicts):
+//   tw[k]       = e^{-2 pi i k / 1024}, k < 512                     (untangling; lane k & 63)
+//   tw1[r][k]   = e^{-2 pi i r k / 64},  r, k < 8                    (pass 1; 8 distinct addresses per instruction)
+//   tw2[r][j]   = e^{-2 pi i r j / 512}, r < 8, j < 64               (pass 2; lane j)
+constexpr int TW_FLOATS = (NB + 64 + 512) * 2;
 
 // Complex numbers as register pairs.  Every swap / negate of a component rides on the operand-select and negate modifiers of
 // the packed instruction that consumes it (hipcc builds such vectors with v_mov / v_xor instead: a third of the kernel's
@@ -75,27 +88,56 @@ __device__ __forceinline__ void dft8(c2 (&v)[8]) {
   dft4<true>(d0, d1, d2, d3, v[1], v[3], v[5], v[7]);
 }
 
-// The three radix-8 Stockham passes of stft1024_kernel (its comments explain the swizzles) as one call: v[r] holds element
-// lane + 64 r on entry and DFT bin lane + 64 r on return (forward transform, e^{-2 pi i k n / 512}); xb is the wave's own
-// 512-point LDS column, tw1 / tw2 the tables stft.hip describes (tw1[r][k] = root 16 r k, tw2[r][j] = root 2 r j of 1024).
+// Entry m (< NFFT, every m once per workgroup) of the three tables, built with sincospi: no global tables, no hidden state.  The
+// pass twiddles are the same 1024-th roots (identical bits to indexing one table): tw1[r][k] = root 16 r k, tw2[r][j] = root
+// 2 r j.  Returns cos(2 pi m / 1024), from which each kernel derives its Hann window at its own scale.
+__device__ __forceinline__ float fft512_fill_tables(c2* tw, c2* tw1, c2* tw2, int m) {
+  float s, c;
+  sincospif((float)m * (1.0f / 512.0f), &s, &c);  // angle = 2 pi m / 1024 = pi * m / 512
+  if (m < NB) tw[m] = c2{c, -s};
+  if (m < 64) {
+    float s1, c1;
+    sincospif((float)(((m >> 3) * (m & 7) * 16) & (NFFT - 1)) * (1.0f / 512.0f), &s1, &c1);
+    tw1[m] = c2{c1, -s1};
+  }
+  if (m < 512) {
+    float s2, c2_;
+    sincospif((float)(((m >> 6) * (m & 63) * 2) & (NFFT - 1)) * (1.0f / 512.0f), &s2, &c2_);
+    tw2[m] = c2{c2_, -s2};
+  }
+  return c;
+}
+
+// The three radix-8 Stockham passes as one call: v[r] holds element lane + 64 r on entry and DFT bin lane + 64 r on return
+// (forward transform, e^{-2 pi i k n / 512}); xb is the wave's own 512-point LDS column, which serves both exchanges: there is
+// no workgroup barrier inside a frame.
 __device__ __forceinline__ void fft512_wave(c2 (&v)[8], c2* xb, const c2* tw1, const c2* tw2, int lane) {
+  // pass 0 (Ns = 1): no twiddles; out[8 j + r]
   dft8(v);
   __builtin_amdgcn_wave_barrier();
+  // Exchange 1: element e = 8 j + r is stored at e ^ ((e >> 4) & 7).  A ds_write_b64 is served in groups of 16 contiguous
+  // lanes over 32 banks (16 eight-byte slots): unswizzled, 8 j + r puts the 16 lanes on 2 slots (8-way conflict); the XOR
+  // with j >> 1 spreads them over all 16.  The reader's e = j + 64 r has (e >> 4) & 7 = ((j >> 4) + 4 r) & 7: constant
+  // per 16 lanes, so its 32-lane groups still read 32 distinct slots.
 #pragma unroll
   for (int r = 0; r < 8; ++r) xb[(8 * lane + r) ^ ((lane >> 1) & 7)] = v[r];
   __builtin_amdgcn_wave_barrier();
+  // pass 1 (Ns = 8): in[j + 64 r] * exp(-2 pi i r k / 64), k = j & 7; out[(j>>3)*64 + k + 8 r]
   {
     const int k = lane & 7;
 #pragma unroll
-    for (int r = 0; r < 8; ++r)
+    for (int r = 0; r < 8; ++r)  // ((lane >> 4) + 4 r) & 7 = (lane >> 4) ^ 4 (r & 1): two base addresses + immediate offsets
       v[r] = cmul(lds_c2(xb + (((lane ^ (lane >> 4)) ^ (4 * (r & 1))) + 64 * r)), lds_c2(tw1 + r * 8 + k));
     dft8(v);
     __builtin_amdgcn_wave_barrier();
-    const int j0 = (lane >> 3) * 64 + k, swz = lane & 8;
+    // Exchange 2: element e = 64 g + k + 8 r (g = j >> 3) is stored at e ^ (8 * (g & 1)): the two g of a 16-lane write group
+    // would share their 8 slots, bit 3 separates them.  The reader's e = j + 64 r sees the constant 8 * (r & 1).
+    const int j0 = (lane >> 3) * 64 + k, swz = lane & 8;  // 8 * (g & 1)
 #pragma unroll
     for (int r = 0; r < 8; ++r) xb[(j0 + 8 * r) ^ swz] = v[r];
     __builtin_amdgcn_wave_barrier();
   }
+  // pass 2 (Ns = 64): in[j + 64 r] * exp(-2 pi i r j / 512); result Z[j + 64 r] stays in lane j, register r
 #pragma unroll
   for (int r = 0; r < 8; ++r) v[r] = cmul(lds_c2(xb + ((lane + 64 * r) ^ (8 * (r & 1)))), lds_c2(tw2 + r * 64 + lane));
   dft8(v);

@@ -235,14 +235,7 @@ __global__ void __launch_bounds__(64) flac_decode_k(flac::Job jb, Frame* __restr
   __shared__ uint16_t table[256];
   __shared__ uint32_t xpow[65];
   const int lane = threadIdx.x;
-  for (int i = lane; i < 256; i += 64) table[i] = (uint16_t)flac::crc16_table_entry((uint32_t)i);
-  {
-    const uint32_t x32 = flac::crc16_mulmod(0x8005, 0x8005);  // x^16 = 0x8005 mod P, squared
-    uint32_t p = 1;
-    for (int k = 0; k < lane; ++k) p = flac::crc16_mulmod(p, x32);
-    xpow[lane] = p;
-    if (lane == 63) xpow[64] = flac::crc16_mulmod(p, x32);
-  }
+  flac::crc16_setup(table, xpow, lane);
   __syncthreads();
   jb.crc_table = table;
   jb.xpow = xpow;

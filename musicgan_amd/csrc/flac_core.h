@@ -153,6 +153,17 @@ FLAC_HD uint32_t crc16_mulmod(uint32_t a, uint32_t b) {
   return r;
 }
 
+// Lane `lane` of 64 fills its share of table[256] (crc16_byte's T) and of xpow[65], xpow[t] = x^(32 t) mod P: what Job::crc_table
+// and Job::xpow point at.  The caller's barrier follows.
+FLAC_HD void crc16_setup(uint16_t* table, uint32_t* xpow, int lane) {
+  for (int i = lane; i < 256; i += 64) table[i] = (uint16_t)crc16_table_entry((uint32_t)i);
+  const uint32_t x32 = crc16_mulmod(0x8005, 0x8005);  // x^16 = 0x8005 mod P, squared
+  uint32_t p = 1;
+  for (int k = 0; k < lane; ++k) p = crc16_mulmod(p, x32);
+  xpow[lane] = p;
+  if (lane == 63) xpow[64] = crc16_mulmod(p, x32);
+}
+
 // ---------------------------------------------------------------- bit reader over the zero-padded region
 // `d` is readable (zero) up to nwords 32-bit words; words at or past nwords read as 0 and set `over`.
 struct Bits {

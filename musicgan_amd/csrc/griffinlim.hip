@@ -6,7 +6,7 @@
 // of FPT = 16 consecutive frames: the 512 x 16 tile of Z is loaded with the lanes along t (128-byte runs of the frequency-major
 // spectrum) and transposed through LDS into one 4 KiB column per frame; one wave inverts one frame in its column -- Hermitian
 // shortcut: the 1024 real samples are the 512-point complex inverse transform of Z'[k] = (X[k] + conj X[512-k]) + i e^{+2 pi i k/1024}
-// (X[k] - conj X[512-k]), evaluated as conj(FFT(conj Z')) with the forward passes and tables of stft.hip -- and leaves the windowed
+// (X[k] - conj X[512-k]), evaluated as conj(FFT(conj Z')) with the forward passes and tables of fft512.h -- and leaves the windowed
 // frame there; then every output sample of the tile's HPT = 13 hops gathers its <= 4 frames from LDS, newest frame first (the order
 // of mg_codec_inv's inv_overlap_add), divides by the window envelope of the frames that exist and is stored once, 16 bytes per lane.
 // No frame buffer in HBM: the three frames in front of a tile are recomputed (3 / 13 more FFT work; their reads of Z hit the L2).
@@ -17,13 +17,8 @@
 
 namespace {
 
-constexpr int NFFT = 1024, HOP = 256, NB = 512;
-constexpr int NWAVE = 8;                 // waves per workgroup
-constexpr int FPW = 2;                   // frames per wave and tile
 constexpr int FPT = NWAVE * FPW;         // frames per tile
 constexpr int HPT = FPT - 3;             // hops of 256 output samples per tile: hop h sums frames h-3 .. h
-constexpr int XSTR = NB + 2;             // column stride in float2 units (stft.hip: conflict-free transposed access)
-constexpr int TW_FLOATS = (NB + 64 + 512) * 2;
 constexpr size_t ISTFT_LDS = (size_t)(TW_FLOATS + NFFT + FPT * XSTR * 2) * sizeof(float);
 constexpr int ZPT = NB * FPT / (64 * NWAVE);  // spectrum values per thread and tile
 
@@ -31,28 +26,13 @@ __global__ void __launch_bounds__(64 * NWAVE, 2) istft1024_kernel(const float2* 
                                                                   int ntiles) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   c2* tw = reinterpret_cast<c2*>(smem);          // e^{-2 pi i k / 1024}, k < 512
-  c2* tw1 = tw + NB;                              // pass tables as in stft.hip
+  c2* tw1 = tw + NB;                              // the pass tables of fft512.h
   c2* tw2 = tw1 + 64;
   float* win = smem + TW_FLOATS;                  // periodic Hann(1024)
   c2* xbuf = reinterpret_cast<c2*>(win + NFFT);   // [FPT][XSTR]: a frame's spectrum, then its exchanges, then its 1024 samples
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (int m = tid; m < NFFT; m += 64 * NWAVE) {
-    float s, c;
-    sincospif((float)m * (1.0f / 512.0f), &s, &c);
-    if (m < NB) tw[m] = c2{c, -s};
-    win[m] = 0.5f - 0.5f * c;
-    if (m < 64) {
-      float s1, c1;
-      sincospif((float)(((m >> 3) * (m & 7) * 16) & (NFFT - 1)) * (1.0f / 512.0f), &s1, &c1);
-      tw1[m] = c2{c1, -s1};
-    }
-    if (m < 512) {
-      float s2, c2_;
-      sincospif((float)(((m >> 6) * (m & 63) * 2) & (NFFT - 1)) * (1.0f / 512.0f), &s2, &c2_);
-      tw2[m] = c2{c2_, -s2};
-    }
-  }
+  for (int m = tid; m < NFFT; m += 64 * NWAVE) win[m] = 0.5f - 0.5f * fft512_fill_tables(tw, tw1, tw2, m);
 
   // tile i writes hops h0 = 2 + HPT i .. h0 + HPT - 1 of the un-trimmed signal (the centre trim drops hops 0 and 1) from the
   // frames tA = h0 - 3 .. tA + FPT - 1; frames before 0 or past TT - 1 do not exist and are left out of sum and envelope.

@@ -213,28 +213,6 @@ __global__ void __launch_bounds__(256) loud_segments_k(const double* __restrict_
   S[(i64)c * nseg + j] = acc;
 }
 
-// the sum over the 256 threads of a workgroup, the same tree on every run; every thread returns the total
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  __syncthreads();  // `red` may still be read from the call before
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int d = 128; d > 0; d >>= 1) {
-    if ((int)threadIdx.x < d) red[threadIdx.x] += red[threadIdx.x + d];
-    __syncthreads();
-  }
-  return red[0];
-}
-__device__ __forceinline__ double block_max(double v, double* red) {
-  __syncthreads();
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int d = 128; d > 0; d >>= 1) {
-    if ((int)threadIdx.x < d) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + d]);
-    __syncthreads();
-  }
-  return red[0];
-}
-
 // mean square of block i (segments i .. i + 3), weighted over the channels
 __device__ __forceinline__ double block_z(const double* __restrict__ S, const Weights& w, int C, i64 nseg, double inv, i64 i) {
   double z = 0.0;
@@ -271,9 +249,9 @@ __global__ void __launch_bounds__(256) loud_gate_k(const double* __restrict__ S,
       cnt += 1.0;
     }
   }
-  sum = block_sum(sum, red);
-  cnt = block_sum(cnt, red);
-  top = block_max(top, red);
+  sum = mg_block_sum_f64(sum, red);
+  cnt = mg_block_sum_f64(cnt, red);
+  top = mg_block_max_f64(top, red);
   if (cnt == 0.0) {
     if (threadIdx.x == 0) {
       record[0] = ninf;
@@ -293,8 +271,8 @@ __global__ void __launch_bounds__(256) loud_gate_k(const double* __restrict__ S,
       cnt2 += 1.0;
     }
   }
-  sum2 = block_sum(sum2, red);
-  cnt2 = block_sum(cnt2, red);
+  sum2 = mg_block_sum_f64(sum2, red);
+  cnt2 = mg_block_sum_f64(cnt2, red);
   if (threadIdx.x == 0) {
     record[0] = cnt2 > 0.0 ? -0.691 + 10.0 * log10(sum2 / cnt2) : ninf;
     record[1] = top;

@@ -81,6 +81,27 @@ __device__ __forceinline__ float mg_wave_sum_to_lane63(float v) {
   return v;
 }
 
+// The float64 sum / maximum over the 256 threads of a workgroup through red[256]: one tree (strides 128 .. 1), the same on every
+// run; every thread returns the result.  The leading barrier makes back-to-back calls on one `red` safe: the result of the call
+// before is read by every thread before any thread overwrites it.
+template <class Op>
+__device__ __forceinline__ double mg_block_reduce_f64(double v, double* red, Op op) {
+  __syncthreads();
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = 128; s >= 1; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] = op(red[threadIdx.x], red[threadIdx.x + s]);
+    __syncthreads();
+  }
+  return red[0];
+}
+__device__ __forceinline__ double mg_block_sum_f64(double v, double* red) {
+  return mg_block_reduce_f64(v, red, [](double a, double b) { return a + b; });
+}
+__device__ __forceinline__ double mg_block_max_f64(double v, double* red) {
+  return mg_block_reduce_f64(v, red, [](double a, double b) { return fmax(a, b); });
+}
+
 // LeakyReLU for 0 < slope <= 1 (every caller: 0.2, or 1 = none): max(v, slope * v) -- one v_mul + one v_max instead of v_cmp +
 // v_mul + v_cndmask (the select alone was measured at 20 cycles against 7.5 for v_max, tools/hwtests/valu_cost.hip); the same bits
 // as `v > 0 ? v : v * slope` for every input incl. signed zeros.

@@ -32,16 +32,6 @@ constexpr int NN_TQ = 2;                       // 16-query tiles per wave
 constexpr int NN_QB = 16 * NN_TQ * 4;          // queries per workgroup of 4 waves
 constexpr int NN_MAXK = 16;
 
-__device__ __forceinline__ double nn_block_sum(double v, double* red) {  // fixed tree over the 256 threads; the sum in thread 0
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = 128; s >= 1; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  return red[0];
-}
-
 __global__ void __launch_bounds__(256) nn_sqnorm_k(const float* __restrict__ x, double* __restrict__ out, long long D) {
   __shared__ double red[256];
   const float* row = x + (size_t)blockIdx.x * D;
@@ -50,7 +40,7 @@ __global__ void __launch_bounds__(256) nn_sqnorm_k(const float* __restrict__ x, 
     const double v = (double)row[i];
     s += v * v;
   }
-  s = nn_block_sum(s, red);
+  s = mg_block_sum_f64(s, red);
   if (threadIdx.x == 0) out[blockIdx.x] = s;
 }
 

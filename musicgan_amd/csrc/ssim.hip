@@ -225,13 +225,8 @@ __global__ void __launch_bounds__(256) ssim_mean_k(const double* __restrict__ va
   __shared__ double red[256];
   double acc = 0.0;
   for (long long i = threadIdx.x; i < n; i += 256) acc += values[i];
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = 128; s >= 1; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = red[0] / (double)n;
+  acc = mg_block_sum_f64(acc, red);
+  if (threadIdx.x == 0) out[0] = acc / (double)n;
 }
 
 size_t ssim_slot_doubles(int64_t N, int C, int H, int W) {

@@ -11,22 +11,12 @@
 #include <cmath>
 
 #include "fft512.h"
+#include "fft_radix2.h"
 #include "mg_common.h"
 
 namespace {
 
-constexpr int NFFT = 1024, HOP = 256, NB = 512;  // NB = complex points = output bins
-constexpr int NWAVE = 8;                          // waves per workgroup
-constexpr int FPW = 2;                            // frames per wave and tile
-constexpr int FPB = NWAVE * FPW;                  // frames per tile: 8 x 8 bytes = one 64-byte run per bin row
-// per-frame LDS column (float2 units).  XSTR = 2 (mod 32): in the transposed read-out the 16 frames of one bin row land on the
-// even 8-byte slots of the 256-byte bank row and the next bin row's on the odd ones, so a 32-lane ds_read_b64 group is conflict-free
-constexpr int XSTR = NB + 2;
-// twiddle tables, each laid out in the order its pass reads it (lane-contiguous or broadcast: no bank conflicts):
-//   tw[k]       = e^{-2 pi i k / 1024}, k < 512                     (untangling; lane k & 63)
-//   tw1[r][k]   = e^{-2 pi i r k / 64},  r, k < 8                    (pass 1; 8 distinct addresses per instruction)
-//   tw2[r][j]   = e^{-2 pi i r j / 512}, r < 8, j < 64               (pass 2; lane j)
-constexpr int TW_FLOATS = (NB + 64 + 512) * 2;
+constexpr int FPB = NWAVE * FPW;  // frames per tile: 8 x 8 bytes = one 64-byte run per bin row
 constexpr size_t STFT_LDS = (size_t)(TW_FLOATS + NFFT + FPB * XSTR * 2) * sizeof(float);
 
 // Persistent workgroups of 8 waves (two per CU: one's write-out runs under the other's FFTs; <= 128 registers): twiddles and window are built once
@@ -81,23 +71,10 @@ __global__ void __launch_bounds__(64 * NWAVE, 2) stft1024_kernel(const void* __r
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (int m = tid; m < NFFT; m += 64 * NWAVE) {
-    float s, c;
-    sincospif((float)m * (1.0f / 512.0f), &s, &c);  // angle = 2 pi m / 1024 = pi * m / 512
-    if (m < NB) tw[m] = c2{c, -s};
+    const float c = fft512_fill_tables(tw, tw1, tw2, m);
     // Hann / sqrt(384) (sum of hann^2 over 1024 = 384), times the 1/2 of the real-FFT untangling: a power-of-two scale
     // commutes exactly with every rounding of the (linear) transform, so it costs nothing here instead of 16 multiplies there
     win[m] = (0.5f - 0.5f * c) * (0.5f * 0.05103103630798288f);
-    // the pass twiddles are the same 1024-th roots (identical bits to indexing one table): tw1[r][k] = root 16 r k, tw2[r][j] = root 2 r j
-    if (m < 64) {
-      float s1, c1;
-      sincospif((float)(((m >> 3) * (m & 7) * 16) & (NFFT - 1)) * (1.0f / 512.0f), &s1, &c1);
-      tw1[m] = c2{c1, -s1};
-    }
-    if (m < 512) {
-      float s2, c2_;
-      sincospif((float)(((m >> 6) * (m & 63) * 2) & (NFFT - 1)) * (1.0f / 512.0f), &s2, &c2_);
-      tw2[m] = c2{c2_, -s2};
-    }
   }
   __syncthreads();
 
@@ -143,36 +120,7 @@ __global__ void __launch_bounds__(64 * NWAVE, 2) stft1024_kernel(const void* __r
         const int tnext = tile + (int)gridDim.x < ntiles ? (tile + (int)gridDim.x) * FPB + wave * FPW : T;
         load_frame(f + 1 < FPW ? t0 + fl + 1 : tnext, xn);
       }
-      // pass 0 (Ns = 1): no twiddles; out[8 j + r]
-      dft8(v);
-      __builtin_amdgcn_wave_barrier();
-      // Exchange 1: element e = 8 j + r is stored at e ^ ((e >> 4) & 7).  A ds_write_b64 is served in groups of 16 contiguous
-      // lanes over 32 banks (16 eight-byte slots): unswizzled, 8 j + r puts the 16 lanes on 2 slots (8-way conflict); the XOR
-      // with j >> 1 spreads them over all 16.  The reader's e = j + 64 r has (e >> 4) & 7 = ((j >> 4) + 4 r) & 7: constant
-      // per 16 lanes, so its 32-lane groups still read 32 distinct slots.
-#pragma unroll
-      for (int r = 0; r < 8; ++r) xb[(8 * lane + r) ^ ((lane >> 1) & 7)] = v[r];
-      __builtin_amdgcn_wave_barrier();
-      // pass 1 (Ns = 8): in[j + 64 r] * exp(-2 pi i r k / 64), k = j & 7; out[(j>>3)*64 + k + 8 r]
-      {
-        const int k = lane & 7;
-#pragma unroll
-        for (int r = 0; r < 8; ++r)  // ((lane >> 4) + 4 r) & 7 = (lane >> 4) ^ 4 (r & 1): two base addresses + immediate offsets
-          v[r] = cmul(lds_c2(xb + (((lane ^ (lane >> 4)) ^ (4 * (r & 1))) + 64 * r)), lds_c2(tw1 + r * 8 + k));
-        dft8(v);
-        __builtin_amdgcn_wave_barrier();
-        // Exchange 2: element e = 64 g + k + 8 r (g = j >> 3) is stored at e ^ (8 * (g & 1)): the two g of a 16-lane write group
-        // would share their 8 slots, bit 3 separates them.  The reader's e = j + 64 r sees the constant 8 * (r & 1).
-        const int j0 = (lane >> 3) * 64 + k, swz = lane & 8;  // 8 * (g & 1)
-#pragma unroll
-        for (int r = 0; r < 8; ++r) xb[(j0 + 8 * r) ^ swz] = v[r];
-        __builtin_amdgcn_wave_barrier();
-      }
-      // pass 2 (Ns = 64): in[j + 64 r] * exp(-2 pi i r j / 512); result Z[j + 64 r] stays in lane j, register r
-#pragma unroll
-      for (int r = 0; r < 8; ++r) v[r] = cmul(lds_c2(xb + ((lane + 64 * r) ^ (8 * (r & 1)))), lds_c2(tw2 + r * 64 + lane));
-      dft8(v);
-      __builtin_amdgcn_wave_barrier();
+      fft512_wave(v, xb, tw1, tw2, lane);
       // untangle: X[k] = (Z[k] + conj Z[512-k])/2 - i/2 * e^{-2 pi i k/1024} * (Z[k] - conj Z[512-k]),  k = lane + 64 r.
       // Z[512-k] sits in lane (64-lane)&63, register 7-r (lane != 0) or 8-r (lane == 0; r == 0 -> Z[0] itself).
       const int src = (64 - lane) & 63;
@@ -257,7 +205,7 @@ static int launch_stft(const void* wav, float* out_re, float* out_im, long long 
 __global__ void __launch_bounds__(256) stft_generic_k(const float* __restrict__ wav, float* __restrict__ out, long long L, int T, int N,
                                                       int lgN, int hop, float inv_norm) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  c2* buf = reinterpret_cast<c2*>(smem);
+  float2* buf = reinterpret_cast<float2*>(smem);
   const int t = blockIdx.x;
   const long long base = (long long)t * hop - N / 2;
   for (int n = threadIdx.x; n < N; n += 256) {
@@ -268,23 +216,11 @@ __global__ void __launch_bounds__(256) stft_generic_k(const float* __restrict__ 
     sincospif(2.0f * (float)n / (float)N, &sn, &cs);
     const float w = (0.5f - 0.5f * cs) * inv_norm;
     // bit-reversed placement: the stages below are decimation in time
-    buf[__brev((unsigned)n) >> (32 - lgN)] = c2{wav[s] * w, 0.f};
+    buf[__brev((unsigned)n) >> (32 - lgN)] = make_float2(wav[s] * w, 0.f);
   }
   __syncthreads();
-  for (int st = 0; st < lgN; ++st) {
-    const int half = 1 << st;
-    for (int i = threadIdx.x; i < N / 2; i += 256) {
-      const int k = i & (half - 1), j = ((i >> st) << (st + 1)) + k;
-      float sn, cs;
-      sincospif((float)k / (float)half, &sn, &cs);  // e^{-i pi k / half}
-      const c2 a = buf[j], b = buf[j + half];
-      const c2 wb = c2{b.x * cs + b.y * sn, b.y * cs - b.x * sn};
-      buf[j] = c2{a.x + wb.x, a.y + wb.y};
-      buf[j + half] = c2{a.x - wb.x, a.y - wb.y};
-    }
-    __syncthreads();
-  }
-  for (int k = threadIdx.x; k < N / 2; k += 256) *reinterpret_cast<c2*>(out + 2 * ((size_t)k * T + t)) = buf[k];
+  fft_radix2_lds(buf, lgN, threadIdx.x, 256, TwForward{});
+  for (int k = threadIdx.x; k < N / 2; k += 256) *reinterpret_cast<float2*>(out + 2 * ((size_t)k * T + t)) = buf[k];
 }
 
 }  // namespace

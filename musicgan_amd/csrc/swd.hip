@@ -81,18 +81,6 @@ __global__ void __launch_bounds__(256) swd_lap_k(const float* __restrict__ x, co
 }
 
 // ------------------------------------------------------------------ gather + statistics
-__device__ __forceinline__ double swd_block_sum(double v, double* red) {  // fixed tree over the 256 threads; the sum in thread 0
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = 128; s >= 1; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
-
 __global__ void __launch_bounds__(256) swd_gather_k(const float* __restrict__ img, const int* __restrict__ centres,
                                                     float* __restrict__ desc, double* __restrict__ stats, int C, int H, int W, int P,
                                                     int p, size_t row0) {
@@ -113,8 +101,8 @@ __global__ void __launch_bounds__(256) swd_gather_k(const float* __restrict__ im
       s += (double)v;
       q += (double)v * (double)v;  // exact: a float32 squared has 48 significant bits
     }
-    s = swd_block_sum(s, red);
-    q = swd_block_sum(q, red);
+    s = mg_block_sum_f64(s, red);
+    q = mg_block_sum_f64(q, red);
     if (threadIdx.x == 0) {
       double* o = stats + ((row0 / P + n) * C + c) * 2;
       o[0] = s;
@@ -133,8 +121,8 @@ __global__ void __launch_bounds__(256) swd_stats_finish_k(const double* __restri
     s += stats[(i * C + c) * 2];
     q += stats[(i * C + c) * 2 + 1];
   }
-  s = swd_block_sum(s, red);
-  q = swd_block_sum(q, red);
+  s = mg_block_sum_f64(s, red);
+  q = mg_block_sum_f64(q, red);
   if (threadIdx.x == 0) {
     const double mean = s / count;
     double var = q / count - mean * mean;
@@ -301,7 +289,7 @@ __global__ void __launch_bounds__(256) swd_absdiff_part_k(const float* __restric
   double acc = 0.0;
   const long long stride = (long long)gridDim.x * 256;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) acc += (double)fabsf(a[i] - b[i]);
-  acc = swd_block_sum(acc, red);
+  acc = mg_block_sum_f64(acc, red);
   if (threadIdx.x == 0) part[blockIdx.x] = acc;
 }
 
@@ -310,7 +298,7 @@ __global__ void __launch_bounds__(256) swd_absdiff_fin_k(const double* __restric
   __shared__ double red[256];
   double acc = 0.0;
   for (int i = threadIdx.x; i < nparts; i += 256) acc += part[i];
-  acc = swd_block_sum(acc, red);
+  acc = mg_block_sum_f64(acc, red);
   if (threadIdx.x == 0) out[0] = (float)(acc / count);
 }
 

@@ -14,7 +14,9 @@
 //   5. overlap (one thread per output frame): window slopes, overlap-add of the two blocks covering the frame, interleave, trim.
 //   6. finalize (one workgroup): the first bad page and the first bad packet, for the host's single status read.
 // Every sum has a fixed order: the same input gives the same bits on every run.
+#include "fft_radix2.h"
 #include "mg_common.h"
+#include "ogg_crc.h"
 
 namespace {
 
@@ -28,7 +30,6 @@ constexpr int IMDCT_THREADS = 256;
 constexpr int MAX_FFT = 2048;  // n / 4 complex points for n = 8192
 constexpr int OLA_THREADS = 256;
 constexpr int FIN_THREADS = 256;
-constexpr uint32_t OGG_POLY = 0x04C11DB7u;
 
 // int32 setup layout (audio/vorbis.py pack_setup)
 constexpr int BOOK_INTS = 8, FLOOR_INTS = 484, RES_INTS = 520, MAP_INTS = 556;
@@ -74,25 +75,6 @@ Layout layout(int64_t npk, int64_t npages, int64_t spec_floats, int ch, int64_t 
 }
 
 // ------------------------------------------------------------------ 1. pages
-__device__ uint32_t gf2_mulmod(uint32_t a, uint32_t b) {  // a * b mod the Ogg polynomial (both as 32-bit remainders)
-  uint32_t r = 0;
-  for (int i = 31; i >= 0; --i) {
-    r = (r << 1) ^ ((r >> 31) ? OGG_POLY : 0u);
-    if ((b >> i) & 1u) r ^= a;
-  }
-  return r;
-}
-
-__device__ uint32_t xpow8(int64_t k) {  // x^(8k) mod P
-  uint32_t r = 1u, sq = 1u << 8;          // x^0, x^8
-  while (k) {
-    if (k & 1) r = gf2_mulmod(r, sq);
-    sq = gf2_mulmod(sq, sq);
-    k >>= 1;
-  }
-  return r;
-}
-
 __global__ void __launch_bounds__(PAGE_THREADS) vorbis_pages_k(const uint8_t* __restrict__ file, const int64_t* __restrict__ pages,
                                                                int64_t crc_from, uint8_t* __restrict__ payload,
                                                                int32_t* __restrict__ page_bad) {
@@ -106,28 +88,8 @@ __global__ void __launch_bounds__(PAGE_THREADS) vorbis_pages_k(const uint8_t* __
     if (t == 0) page_bad[pg] = 0;
     return;
   }
-  {
-    uint32_t r = (uint32_t)t << 24;
-    for (int k = 0; k < 8; ++k) r = (r & 0x80000000u) ? (r << 1) ^ OGG_POLY : (r << 1);
-    T[t] = r;
-  }
-  __syncthreads();
-  const int64_t len = body + blen - off;
-  const int64_t chunk = (len + PAGE_THREADS - 1) / PAGE_THREADS;
-  const int64_t a = (int64_t)t * chunk, b = a + chunk < len ? a + chunk : len;
-  uint32_t c = 0;
-  for (int64_t i = a; i < b; ++i) {
-    const uint32_t byte = (i >= 22 && i < 26) ? 0u : file[off + i];
-    c = (c << 8) ^ T[((c >> 24) ^ byte) & 0xFF];
-  }
-  if (a < b && b < len) c = gf2_mulmod(c, xpow8(len - b));  // shift past the bytes after this chunk
-  if (a >= b) c = 0;
-  for (int s = 32; s >= 1; s >>= 1) c ^= (uint32_t)__shfl_xor((int)c, s, 64);
-  if ((t & 63) == 0) part[t >> 6] = c;
-  __syncthreads();
+  const uint32_t x = ogg::page_crc_block<PAGE_THREADS>(file + off, body + blen - off, t, T, part);
   if (t == 0) {
-    uint32_t x = 0;
-    for (int w = 0; w < PAGE_THREADS / 64; ++w) x ^= part[w];
     const uint32_t stored = (uint32_t)file[off + 22] | ((uint32_t)file[off + 23] << 8) | ((uint32_t)file[off + 24] << 16) |
                             ((uint32_t)file[off + 25] << 24);
     page_bad[pg] = x != stored;
@@ -510,34 +472,7 @@ __global__ void __launch_bounds__(IMDCT_THREADS) vorbis_imdct_k(const int64_t* _
   const float2* post = pre + H;
   const float2* w = post + H;
   float* X = ws.spec + pk[p * PK + 2] + (int64_t)c * M;
-  const int lg = 31 - __clz(H);
-  for (int t = threadIdx.x; t < H; t += IMDCT_THREADS) {
-    const float re = X[2 * t], im = X[M - 1 - 2 * t];
-    const float2 q = pre[t];
-    const int r = (int)(__brev((uint32_t)t) >> (32 - lg));
-    buf[r] = make_float2(re * q.x - im * q.y, re * q.y + im * q.x);
-  }
-  __syncthreads();
-  for (int len = 2; len <= H; len <<= 1) {
-    const int half = len >> 1;
-    const int stride = H / len;
-    for (int j = threadIdx.x; j < H / 2; j += IMDCT_THREADS) {
-      const int g = j / half, k = j - g * half;
-      const int i0 = g * len + k, i1 = i0 + half;
-      const float2 tw1 = w[k * stride];
-      const float2 b = buf[i1];
-      const float2 t = make_float2(b.x * tw1.x - b.y * tw1.y, b.x * tw1.y + b.y * tw1.x);
-      const float2 a = buf[i0];
-      buf[i0] = make_float2(a.x + t.x, a.y + t.y);
-      buf[i1] = make_float2(a.x - t.x, a.y - t.y);
-    }
-    __syncthreads();
-  }
-  for (int s = threadIdx.x; s < H; s += IMDCT_THREADS) {
-    const float2 v = buf[s], q = post[s];
-    X[2 * s] = v.x * q.x - v.y * q.y;
-    X[M - 1 - 2 * s] = -(v.x * q.y + v.y * q.x);
-  }
+  dct4_lds(X, X, buf, M, pre, post, w, 1.0f, threadIdx.x, IMDCT_THREADS);
 }
 
 // ------------------------------------------------------------------ 5. window, overlap-add, interleave, trim

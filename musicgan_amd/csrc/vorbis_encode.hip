@@ -19,7 +19,9 @@
 //   5. pages (one workgroup per page): header, lacing values, body gathered from the packets, CRC-32 from lane-parallel partial
 //      CRCs shifted into place with a GF(2) multiply.
 // Every sum has a fixed order and no float atomics are used: the same input gives the same bytes on every run.
+#include "fft_radix2.h"
 #include "mg_common.h"
+#include "ogg_crc.h"
 
 namespace {
 
@@ -36,7 +38,6 @@ constexpr int MAX_ITER = 24, FORCE_ITER = 16;
 constexpr float MASK_GAIN = 0.1f;  // 10^(-MASK_DB / 20), MASK_DB = 20 (audio/vorbis_encode.py)
 constexpr int A_THREADS = 256, P_THREADS = 256, L_THREADS = 512, G_THREADS = 256;
 constexpr int PAGE_SEGS = 255, PAGE_BYTES = 4096;
-constexpr uint32_t OGG_POLY = 0x04C11DB7u;
 constexpr uint32_t SERIAL = 0x4D47414Eu;  // audio/vorbis_encode.py SERIAL
 
 // int32 table (audio/vorbis_encode.py TI_*)
@@ -155,36 +156,9 @@ __global__ void __launch_bounds__(A_THREADS) venc_analysis_k(Input in, const int
   if (t < MAX_POSTS) imax[t] = 0;
   if (t == 0) viol = 0, nonzero = 0, first_bad = N2;
   __syncthreads();
-  // DCT-IV (the decoder's routine): pre-twiddle into bit-reversed order, radix-2 FFT, post-twiddle; scaled by 1/512 (= 4 / n)
-  const float2* pre = reinterpret_cast<const float2*>(tf + TF_PRE);
-  const float2* post = reinterpret_cast<const float2*>(tf + TF_POST);
-  const float2* w = reinterpret_cast<const float2*>(tf + TF_FFT);
-  for (int k = t; k < FFT_H; k += A_THREADS) {
-    const float re = u[2 * k], im = u[N2 - 1 - 2 * k];
-    const float2 q = pre[k];
-    const int r = (int)(__brev((uint32_t)k) >> (32 - 9));
-    buf[r] = make_float2(re * q.x - im * q.y, re * q.y + im * q.x);
-  }
-  __syncthreads();
-  for (int len = 2; len <= FFT_H; len <<= 1) {
-    const int half = len >> 1, stride = FFT_H / len;
-    for (int j = t; j < FFT_H / 2; j += A_THREADS) {
-      const int g = j / half, k = j - g * half;
-      const int i0 = g * len + k, i1 = i0 + half;
-      const float2 tw1 = w[k * stride];
-      const float2 b = buf[i1];
-      const float2 tt = make_float2(b.x * tw1.x - b.y * tw1.y, b.x * tw1.y + b.y * tw1.x);
-      const float2 a = buf[i0];
-      buf[i0] = make_float2(a.x + tt.x, a.y + tt.y);
-      buf[i1] = make_float2(a.x - tt.x, a.y - tt.y);
-    }
-    __syncthreads();
-  }
-  for (int s = t; s < FFT_H; s += A_THREADS) {
-    const float2 v = buf[s], q = post[s];
-    X[2 * s] = (v.x * q.x - v.y * q.y) * (1.f / 512.f);
-    X[N2 - 1 - 2 * s] = -(v.x * q.y + v.y * q.x) * (1.f / 512.f);
-  }
+  // DCT-IV, scaled by 1/512 (= 4 / n)
+  dct4_lds(u, X, buf, N2, reinterpret_cast<const float2*>(tf + TF_PRE), reinterpret_cast<const float2*>(tf + TF_POST),
+           reinterpret_cast<const float2*>(tf + TF_FFT), 1.f / 512.f, t, A_THREADS);
   __syncthreads();
   // largest |X| between each pair of neighbouring posts (non-negative floats order as their bits)
   for (int b = t; b < N2; b += A_THREADS) atomicMax(&imax[ti[TI_BIN + b]], __float_as_int(fabsf(X[b])));
@@ -585,25 +559,6 @@ __global__ void __launch_bounds__(L_THREADS) venc_layout_k(Ws ws, int64_t P, int
 }
 
 // ------------------------------------------------------------------ 5. pages
-__device__ uint32_t gf2_mulmod(uint32_t a, uint32_t b) {  // a * b mod the Ogg polynomial
-  uint32_t r = 0;
-  for (int i = 31; i >= 0; --i) {
-    r = (r << 1) ^ ((r >> 31) ? OGG_POLY : 0u);
-    if ((b >> i) & 1u) r ^= a;
-  }
-  return r;
-}
-
-__device__ uint32_t xpow8(int64_t k) {  // x^(8k) mod P
-  uint32_t r = 1u, sq = 1u << 8;
-  while (k) {
-    if (k & 1) r = gf2_mulmod(r, sq);
-    sq = gf2_mulmod(sq, sq);
-    k >>= 1;
-  }
-  return r;
-}
-
 __global__ void __launch_bounds__(G_THREADS) venc_pages_k(Ws ws, int64_t P, int64_t n, int first_seq, uint8_t* __restrict__ out) {
   __shared__ uint32_t T[256];
   __shared__ uint32_t part[G_THREADS / 64];
@@ -642,26 +597,9 @@ __global__ void __launch_bounds__(G_THREADS) venc_pages_k(Ws ws, int64_t P, int6
     }
     o[27 + ns + (b - b0)] = ws.payload[ws.ppay[lo] + (b - ws.plog[lo])];
   }
-  {
-    uint32_t r = (uint32_t)t << 24;
-    for (int k = 0; k < 8; ++k) r = (r & 0x80000000u) ? (r << 1) ^ OGG_POLY : (r << 1);
-    T[t] = r;
-  }
-  __threadfence_block();
-  __syncthreads();
-  const int64_t len = 27 + ns + (b1 - b0);
-  const int64_t chunk = (len + G_THREADS - 1) / G_THREADS;
-  const int64_t a = (int64_t)t * chunk, b = a + chunk < len ? a + chunk : len;
-  uint32_t c = 0;
-  for (int64_t i = a; i < b; ++i) c = (c << 8) ^ T[((c >> 24) ^ o[i]) & 0xFF];
-  if (a < b && b < len) c = gf2_mulmod(c, xpow8(len - b));  // shift past the bytes after this chunk
-  if (a >= b) c = 0;
-  for (int s = 32; s >= 1; s >>= 1) c ^= (uint32_t)__shfl_xor((int)c, s, 64);
-  if ((t & 63) == 0) part[t >> 6] = c;
-  __syncthreads();
+  __threadfence_block();  // the page as the other threads wrote it
+  const uint32_t x = ogg::page_crc_block<G_THREADS>(o, 27 + ns + (b1 - b0), t, T, part);
   if (t == 0) {
-    uint32_t x = 0;
-    for (int k = 0; k < G_THREADS / 64; ++k) x ^= part[k];
     o[22] = (uint8_t)x, o[23] = (uint8_t)(x >> 8), o[24] = (uint8_t)(x >> 16), o[25] = (uint8_t)(x >> 24);
   }
 }
