@@ -910,6 +910,28 @@ size_t mg_polyk_ws_bytes(int64_t subsets, int64_t ma, int64_t mb);
 int mg_polyk_rowsums(const float* a, int64_t na, const float* b, int64_t nb, const int32_t* ia, const int32_t* ib, int64_t subsets,
                      int64_t ma, int64_t mb, int64_t d, int skip_diag, double* out, void* ws, size_t ws_bytes, mg_stream_t stream);
 
+/* ---- mel power spectrogram of waveforms and pooled log rows (csrc/melspec.hip): the kernels behind mel_ops.mel_power,
+ * mel_ops.logmel_pool, audio.mel_spectrogram and metrics.WaveLogMel, which the reference does not have (definition and error bound:
+ * DESIGN.md 4.21).
+ * mel_power: wave holds `rows` signals of `length` float32 mono samples, row_stride >= length samples apart; length > 512; weight
+ *   (bands, 512) float32 on the device; lo, hi: HOST arrays of `bands` bin limits, 0 <= lo <= hi <= 512, read before the call returns
+ *   and passed to the kernel by value (MG_EINVAL otherwise: no index depends on device memory); bands <= 256.  With
+ *   T = 1 + length / 256 and X[k,t] the value of mg_stft_1024 for the row (reflect padding by 512, periodic Hann / sqrt(384),
+ *   k = 0 .. 511, Nyquist dropped):
+ *     p[k,t] = re re + im im                                          float32, every operation rounded, no fma
+ *     s[m,t] = sum_{k = lo[m]}^{hi[m]-1} weight[m,k] p[k,t]           float32, ascending k from +0.0, product and sum rounded apart
+ *   out (rows, bands, T) float32, every element written (an empty band: +0.0); weights outside [lo, hi) are not read.  One launch
+ *   on `stream`; the spectrum is never written; no workspace, no atomics, capturable.  A row of out depends on its signal alone.
+ * logmel_pool: power (rows, bands, frames) float32; windows of `win` frames every `hop` frames, W = (frames - win) / hop + 1 per
+ *   row (win <= frames; the tail is dropped); `pools` divides win; floor > 0.  out (rows W, bands pools) float32, every element written:
+ *     out[b W + n, m pools + j] = (float)(sum of log((double)power[b,m,t] + floor) over the win / pools frames
+ *                                         t = n hop + j win / pools .. of pool j, in ascending t, / (win / pools))
+ *   in float64, rounded once.  One launch, one thread per number, no workspace, no atomics, capturable. */
+int mg_mel_power(const float* wave, int64_t rows, int64_t length, int64_t row_stride, const float* weight, const int32_t* lo,
+                 const int32_t* hi, int bands, float* out, mg_stream_t stream);
+int mg_logmel_pool(const float* power, int64_t rows, int bands, int64_t frames, int win, int hop, int pools, double floor, float* out,
+                   mg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

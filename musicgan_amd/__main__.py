@@ -1,5 +1,5 @@
 """`python -m musicgan_amd <mode> ...`: the reference's four sub-commands with its positional names and flags
-(/root/reference/music_gan/__main__.py:11-124) and `evaluate`, `loudness`, `separate`, `project` and `evaluate_mel`, which the reference does not have, declared as data and dispatched
+(/root/reference/music_gan/__main__.py:11-124) and `evaluate`, `loudness`, `separate`, `project`, `evaluate_mel` and `evaluate_audio`, which the reference does not have, declared as data and dispatched
 lazily (importing `train` pulls in the GPU library, `view_audio` pulls in matplotlib)."""
 import argparse
 import importlib
@@ -218,6 +218,25 @@ _LATENT_MODES = {
                        **({"griffin_lim": a.griffin_lim} if a.griffin_lim else {}),
                        **({"resample": True} if a.resample else {}))),
 }
+# sub-commands that compare two sets of audio files, with no model involved (same declaration; kept apart as well)
+_FILE_SET_MODES = {
+    "evaluate_audio": ("evaluate_audio", "evaluate_audio", [
+        (("real_path",), dict(type=str, metavar="REAL_GLOB", help="the reference set, can be \"real/*.flac\" (any format that can be "
+                                                                  "read: wav, aiff, au, flac, ogg)")),
+        (("fake_path",), dict(type=str, metavar="OTHER_GLOB", help="the set to be judged, can be \"gen/*.wav\"")),
+        (("-n", "--nb-windows"), dict(dest="nb_windows", type=int, default=8192,
+                                      help="windows of 512 frames (2.97 s) per set (clipped to what the files hold)")),
+        (("--seed",), dict(type=int, default=0)),
+        (("--resample",), dict(action="store_true", help="resample files that are not at 44.1 kHz (else they are left out)")),
+        (("-o", "--output"), dict(type=str, default=None, help="also write the result as JSON to this file")),
+        (("--metrics",), dict(type=_mel_metric_list, default=None, metavar="fd,nn,prdc,ndb,kid",
+                              help="evaluate_mel's metrics and keys between the windows of the two sets of files, in the log-mel "
+                                   "spectrogram of the waveforms (default: fd); the _real figures compare two halves of REAL_GLOB")),
+    ], lambda a: (a.real_path, a.fake_path),
+        lambda a: dict(nb_windows=a.nb_windows, seed=a.seed, output=a.output,
+                       **({"metrics": a.metrics} if a.metrics is not None else {}),
+                       **({"resample": True} if a.resample else {}))),
+}
 # sub-commands that evaluate a checkpoint in a feature space other than pixels (same declaration; kept apart as well)
 _FEATURE_MODES = {
     "evaluate_mel": ("evaluate_mel", "evaluate_mel", [
@@ -236,14 +255,21 @@ _FEATURE_MODES = {
                                    "scores; nn, prdc, ndb: as in evaluate, on log-mel rows instead of pixels; kid: the Kernel "
                                    "Inception Distance on the rows of fd (mean and deviation over 100 subsets of 1000, kid_full on "
                                    "all images, kid_real for two halves of the data): unbiased, so comparable across set sizes")),
+        (("--waveform",), dict(action="store_true",
+                               help="take every row from the waveform its image decodes to instead of from the magnitude channel, "
+                                    "so that the phase channel counts (level 7 only); the lines say \"in waveform log-mel space\"")),
+        (("--griffin-lim",), dict(dest="griffin_lim", type=int, default=0, metavar="N",
+                                  help="with --waveform: N rounds of Griffin-Lim phase refinement on every generated image before "
+                                       "it is scored, as generate --griffin-lim N writes it (default 0: none)")),
     ], lambda a: (a.gen_dict_state, a.rand_channels, a.input_dataset),
         lambda a: dict(level=a.level, nb_images=a.nb_images, batch_size=a.batch_size, seed=a.seed, output=a.output,
-                       **({"metrics": a.metrics} if a.metrics is not None else {}))),
+                       **({"metrics": a.metrics} if a.metrics is not None else {}),
+                       **({"griffin_lim": a.griffin_lim} if a.griffin_lim else {}))),
 }
 
 
 def _all_modes() -> dict:
-    return {**_MODES, **_FILE_MODES, **_LATENT_MODES, **_FEATURE_MODES}
+    return {**_MODES, **_FILE_MODES, **_LATENT_MODES, **_FILE_SET_MODES, **_FEATURE_MODES}
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -262,10 +288,14 @@ def build_parser() -> argparse.ArgumentParser:
 def main(argv=None) -> None:
     parser = build_parser()
     args = parser.parse_args(argv)
+    if args.mode == "evaluate_mel" and args.griffin_lim and not args.waveform:
+        parser.error("--griffin-lim needs --waveform")
     if args.mode == "generate" and args.loudness is None and (
             args.limiter or args.limiter_attack is not None or args.limiter_release is not None):
         parser.error("--limiter, --limiter-attack and --limiter-release need --loudness")
     module, function, _, call_args, *call_kwargs = _all_modes()[args.mode]
+    if args.mode == "evaluate_mel" and args.waveform:
+        function = "evaluate_mel_waveform"   # the same arguments, rows from the decoded waveforms (and griffin_lim)
     kwargs = call_kwargs[0](args) if call_kwargs else {}
     getattr(importlib.import_module(f".{module}", __package__), function)(*call_args(args), **kwargs)
 

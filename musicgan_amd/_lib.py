@@ -252,6 +252,8 @@ SIGNATURES = {
     "mg_ola_stretch": (c_int, [_P, c_int64, _P, c_int64, c_int, c_int, _P]),
     "mg_logmel_rows": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, POINTER(ctypes.c_int32), POINTER(ctypes.c_int32), c_int,
                                ctypes.c_double, c_int, _P, _P]),
+    "mg_mel_power": (c_int, [_P, c_int64, c_int64, c_int64, _P, POINTER(ctypes.c_int32), POINTER(ctypes.c_int32), c_int, _P, _P]),
+    "mg_logmel_pool": (c_int, [_P, c_int64, c_int, c_int64, c_int, c_int, c_int, ctypes.c_double, _P, _P]),
     "mg_moments_ws_bytes": (c_size_t, [c_int64, c_int64]),
     "mg_moments": (c_int, [_P, c_int64, c_int64, _P, _P, _P, c_size_t, _P]),
     "mg_standardise_rows": (c_int, [_P, c_int64, c_int64, _P, _P, _P, _P]),

@@ -10,7 +10,7 @@ from typing import Tuple
 import torch as th
 
 from . import constant, wavio
-from .. import gl_ops, hpss_ops, lim_ops, loud_ops, ops, pv_ops
+from .. import gl_ops, hpss_ops, lim_ops, loud_ops, mel_ops, ops, pv_ops
 
 _bark_cache = {}
 
@@ -56,6 +56,42 @@ def stft_from_waveform(raw_audio: th.Tensor, nperseg: int = constant.N_FFT, stri
         return ops.stft_1024_pcm(frames) if fast else ops.stft_generic(ops.pcm_to_mono(frames), nperseg, stride)
     mono = x.reshape(-1).contiguous()
     return ops.stft_1024(mono) if fast else ops.stft_generic(mono, nperseg, stride)
+
+
+_mel_banks = {}
+
+
+def _mel_bank(n_mels: int, f_min: float, f_max: float, device):
+    """(weight on `device`, lo, hi on the host) of metrics.mel_filterbank over the 512 bins, built once per bank and device"""
+    key = (n_mels, float(f_min), float(f_max), str(device))
+    if key not in _mel_banks:
+        from ..metrics import mel_filterbank   # (metrics imports this module's codec vector lazily too)
+        weight, lo, hi = mel_filterbank(constant.N_FFT // 2, n_mels, f_min, f_max)
+        _mel_banks[key] = (weight.to(device), lo, hi)
+    return _mel_banks[key]
+
+
+def mel_spectrogram(waveform: th.Tensor, n_mels: int = 64, f_min: float = 0.0, f_max: float = 22050.0) -> th.Tensor:
+    """(..., L) or (L,) samples at 44.1 kHz, L > 512, any float type, any device -> (..., n_mels, 1 + L // 256) float32 on the GPU:
+    the mel power spectrogram, one fused launch (csrc/melspec.hip; the spectrum is never written).  It restates
+    torchaudio.transforms.MelSpectrogram(sample_rate=44100, n_fft=1024, hop_length=256, power=2, normalized="window",
+    mel_scale="htk", norm=None, f_min=f_min, f_max=f_max, n_mels=n_mels): reflect padding by 512, periodic Hann / sqrt(sum w^2),
+    |X|^2, and the triangular HTK bank metrics.mel_filterbank(512, n_mels, f_min, f_max) over the bins 0 .. 511.  The Nyquist bin is
+    dropped, as everywhere in the codec: its frequency is 22 050 Hz, so for any f_max <= 22050 its weight in every band is 0 and
+    nothing is lost.  torchaudio is not installed where this was written; the tests hold the function against a float64 restatement
+    of the formula (tests/melspec_ref.py), not against torchaudio itself.  Rows are independent: a multi-channel waveform is NOT
+    averaged to mono (the loaders do that), every channel gets its own spectrogram."""
+    if not isinstance(waveform, th.Tensor) or waveform.dim() < 1 or not waveform.is_floating_point():
+        raise ValueError("mel_spectrogram: a floating-point waveform (..., L) expected")
+    if waveform.shape[-1] <= constant.N_FFT // 2 or waveform.numel() == 0:
+        raise ValueError(f"mel_spectrogram: more than {constant.N_FFT // 2} samples per row expected, got {tuple(waveform.shape)}")
+    from ..metrics import mel_filterbank
+    mel_filterbank(constant.N_FFT // 2, n_mels, f_min, f_max)   # refuses a bad bank before a device is looked at
+    dev = waveform.device if waveform.is_cuda else _device()
+    weight, lo, hi = _mel_bank(n_mels, f_min, f_max, dev)
+    rows = waveform.to(dev, th.float32).reshape(-1, waveform.shape[-1]).contiguous()
+    out = mel_ops.mel_power(rows, weight, lo, hi)
+    return out.reshape(*waveform.shape[:-1], n_mels, out.shape[-1])
 
 
 def resample(waveform: th.Tensor, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99,

@@ -13,6 +13,7 @@
 #include "fft512.h"
 #include "fft_radix2.h"
 #include "mg_common.h"
+#include "stft_frame.h"
 
 namespace {
 
@@ -23,41 +24,7 @@ constexpr size_t STFT_LDS = (size_t)(TW_FLOATS + NFFT + FPB * XSTR * 2) * sizeof
 // per workgroup, then each tile of 16 consecutive frames is transformed -- one wave = 2 frames, each in its own 4 KiB LDS column
 // that serves the two Stockham exchanges and finally holds the frame's 512 output bins, so there is no workgroup barrier inside
 // a frame -- and the 16 columns are read out transposed so that every global store instruction writes four 128-byte runs along t.
-// PCM: what `wav` holds -- 0: float32 samples, 1: int16 (scaled by 1/32768 as torchaudio.load(normalize=True) does);  CH: 1 = mono,
-// 2 = interleaved stereo frames as a WAV file stores them, averaged on the way in (functions.py:49: raw_audio.mean(0)) -- a
-// file's bytes go to the GPU as they are and the de-interleave / scale / mono mean cost no pass of their own.
-template <int PCM, int CH>
-struct PcmSrc {
-  // two consecutive mono samples s, s + 1 (s even: aligned loads of 4 .. 16 bytes)
-  static __device__ __forceinline__ c2 pair(const void* __restrict__ w, long long s) {
-    if constexpr (PCM == 0 && CH == 1) {
-      return *reinterpret_cast<const c2*>(reinterpret_cast<const float*>(w) + s);
-    } else if constexpr (PCM == 0) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(w) + 2 * s);
-      return c2{(v[0] + v[1]) / 2.0f, (v[2] + v[3]) / 2.0f};
-    } else if constexpr (CH == 1) {
-      const short2 v = *reinterpret_cast<const short2*>(reinterpret_cast<const short*>(w) + s);
-      return c2{(float)v.x / 32768.0f, (float)v.y / 32768.0f};
-    } else {
-      const short4 v = *reinterpret_cast<const short4*>(reinterpret_cast<const short*>(w) + 2 * s);
-      return c2{((float)v.x / 32768.0f + (float)v.y / 32768.0f) / 2.0f, ((float)v.z / 32768.0f + (float)v.w / 32768.0f) / 2.0f};
-    }
-  }
-  static __device__ __forceinline__ float one(const void* __restrict__ w, long long s) {
-    if constexpr (PCM == 0 && CH == 1) {
-      return reinterpret_cast<const float*>(w)[s];
-    } else if constexpr (PCM == 0) {
-      const float2 v = *reinterpret_cast<const float2*>(reinterpret_cast<const float*>(w) + 2 * s);
-      return (v.x + v.y) / 2.0f;
-    } else if constexpr (CH == 1) {
-      return (float)reinterpret_cast<const short*>(w)[s] / 32768.0f;
-    } else {
-      const short2 v = *reinterpret_cast<const short2*>(reinterpret_cast<const short*>(w) + 2 * s);
-      return ((float)v.x / 32768.0f + (float)v.y / 32768.0f) / 2.0f;
-    }
-  }
-};
-
+// PcmSrc<PCM, CH> (stft_frame.h): the file's bytes go to the GPU as they are, int16 or float32, mono or interleaved stereo.
 template <int PCM, int CH>
 __global__ void __launch_bounds__(64 * NWAVE, 2) stft1024_kernel(const void* __restrict__ wav, float* __restrict__ out_re,
                                                               float* __restrict__ out_im, long long L, int T, int ntiles) {
@@ -72,38 +39,14 @@ __global__ void __launch_bounds__(64 * NWAVE, 2) stft1024_kernel(const void* __r
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (int m = tid; m < NFFT; m += 64 * NWAVE) {
     const float c = fft512_fill_tables(tw, tw1, tw2, m);
-    // Hann / sqrt(384) (sum of hann^2 over 1024 = 384), times the 1/2 of the real-FFT untangling: a power-of-two scale
-    // commutes exactly with every rounding of the (linear) transform, so it costs nothing here instead of 16 multiplies there
-    win[m] = (0.5f - 0.5f * c) * (0.5f * 0.05103103630798288f);
+    win[m] = stft_window_entry(c);
   }
   __syncthreads();
 
   // Samples of a frame, 8 complex pairs per lane: requested one frame ahead (the next frame of the tile, or the first frame
   // of the workgroup's next tile before the write-out of this one), so the HBM latency runs under a whole frame of FFT work
   // instead of in front of it (a wave has nothing else to do: 4 waves per SIMD do not hide ~2500 cycles).
-  auto load_frame = [&](int t, c2 (&x)[8]) {
-    if (t < T) {
-      const long long base = (long long)t * HOP - NFFT / 2;  // sample index of padded position 0 of this frame
-      const bool interior = (base >= 0) && (base + NFFT <= L);
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        const int n = 2 * (lane + 64 * r);
-        if (interior) {
-          x[r] = Src::pair(wav, base + n);
-        } else {
-          long long s0 = base + n, s1 = base + n + 1;
-          if (s0 < 0) s0 = -s0;
-          if (s1 < 0) s1 = -s1;
-          if (s0 >= L) s0 = 2 * (L - 1) - s0;
-          if (s1 >= L) s1 = 2 * (L - 1) - s1;
-          x[r] = c2{Src::one(wav, s0), Src::one(wav, s1)};
-        }
-      }
-    } else {
-#pragma unroll
-      for (int r = 0; r < 8; ++r) x[r] = c2{0.f, 0.f};
-    }
-  };
+  auto load_frame = [&](int t, c2 (&x)[8]) { stft_load_frame<Src>(wav, L, T, t, lane, true, x); };
 
   c2 xn[8];  // the frame in flight
   if ((int)blockIdx.x < ntiles) load_frame(blockIdx.x * FPB + wave * FPW, xn);
@@ -114,32 +57,13 @@ __global__ void __launch_bounds__(64 * NWAVE, 2) stft1024_kernel(const void* __r
       const int fl = wave * FPW + f;  // frame slot in the tile
       c2* xb = xbuf + fl * XSTR;
       c2 v[8];
-#pragma unroll
-      for (int r = 0; r < 8; ++r) v[r] = xn[r] * lds_c2(reinterpret_cast<const c2*>(win + 2 * (lane + 64 * r)));
+      stft_apply_window(xn, win, lane, v);
       {  // one call site: next frame of this tile, first frame of the next tile, or nothing (t = T reads as zeros)
         const int tnext = tile + (int)gridDim.x < ntiles ? (tile + (int)gridDim.x) * FPB + wave * FPW : T;
         load_frame(f + 1 < FPW ? t0 + fl + 1 : tnext, xn);
       }
       fft512_wave(v, xb, tw1, tw2, lane);
-      // untangle: X[k] = (Z[k] + conj Z[512-k])/2 - i/2 * e^{-2 pi i k/1024} * (Z[k] - conj Z[512-k]),  k = lane + 64 r.
-      // Z[512-k] sits in lane (64-lane)&63, register 7-r (lane != 0) or 8-r (lane == 0; r == 0 -> Z[0] itself).
-      const int src = (64 - lane) & 63;
-      c2 zc[8];  // Z[512-k]
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        // value this lane must SEND for the receiver's register r: receiver lane l' = (64-lane)&63 wants register
-        // (l' == 0 ? 8-r : 7-r) of its source lane; every lane != 0 is read by a lane != 0 (7-r); lane 0 reads itself.
-        const c2 send_n0 = v[7 - r];
-        const c2 send_0 = v[(8 - r) & 7];
-        const c2 send = (lane == 0) ? send_0 : send_n0;
-        zc[r] = c2{__shfl(send.x, src), __shfl(send.y, src)};  // Z[512-k] (conjugated by the consumers; the 1/2 is in the window)
-      }
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        const int k = lane + 64 * r;
-        const c2 wd = cmul(lds_c2(tw + k), sub_conj(v[r], zc[r]));
-        xb[k] = add_mi(add_conj(v[r], zc[r]), wd);  // e - i * wd  (pass 2 has read the column: the exchanges are done with it)
-      }
+      stft_untangle(v, xb, tw, lane);  // the frame's 512 bins, left in its column
     }
     __syncthreads();
     // transposed write-out: the 16 frames of one bin row per 8 lanes, two frames (16 bytes) per lane -- stores are issue-bound per

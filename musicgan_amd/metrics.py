@@ -71,7 +71,12 @@ kernels: csrc/kid.hip through musicgan_amd/kid_ops.py -- no kernel matrix is sto
     for batch in fake:  kid.feed_fake(rows(batch))
     kid.result()                                  # {"kid": .., "kid_std": .., "kid_full": ..}; rows standardised by the real moments
     kid.per_sample()                              # (n_fake,) float64 cuda: the witness function at every generated row
-    poly_mmd2(x, y)                               # the estimate for two row tensors as they are"""
+    poly_mmd2(x, y)                               # the estimate for two row tensors as they are
+
+(8) The same rows taken from waveforms, where the phase counts: WaveLogMel.  Definition and error bound: DESIGN.md 4.21; kernels:
+csrc/melspec.hip through mel_ops.mel_power and mel_ops.logmel_pool.
+
+    rows = WaveLogMel(pools=8)(waves)             # (B, L) float32 cuda -> (B * W, 64 * 8): a row per window of 512 frames"""
 from __future__ import annotations
 
 import math
@@ -840,6 +845,57 @@ class LogMel:
             self._dev[x.device] = (self.scale.to(x.device), self.weight.to(x.device))
         scale, weight = self._dev[x.device]
         return mel_ops.logmel_rows(x, 0, scale, weight, self.lo, self.hi, self.floor, self.pools)
+
+
+class WaveLogMel:
+    """The pooled log-mel rows of waveforms: LogMel's feature space taken from the sound instead of from an image's channel 0, so that
+    the phase counts.  A waveform (B, L) at 44.1 kHz is framed as the codec frames it (1024 / 256, reflect padding,
+    periodic Hann / sqrt(384)), |X|^2 is weighted by mel_filterbank(512, bands, f_min, f_max), and log(. + floor) is averaged over
+    window / pools frames per pool, for every window of `window` frames at every `hop` frames (the tail is dropped).  Defaults: 64
+    bands, 32 pools, windows of 512 frames every 512 -- what a 512 x 512 image spans; 130 816 samples are exactly one window.
+
+    `floor` = 1e-6 is the same unmeasured default as LogMel's: no corpus was used to choose it.
+
+        rows = WaveLogMel()(waves)                # (B, L) float32 cuda -> (B * W, 64 * 32) float32 cuda, W = (1 + L // 256 - 512) // 512 + 1
+
+    Two launches of csrc/melspec.hip per call (mel power, then pooling); a row depends on its window's samples alone."""
+
+    def __init__(self, bands: int = 64, pools: int = 32, window: int = 512, hop: int = 512, f_min: float = 0.0,
+                 f_max: float = 22050.0, floor: float = 1e-6) -> None:
+        for name, v in (("pools", pools), ("window", window), ("hop", hop)):
+            if not _is_int(v) or v < 1:
+                raise ValueError(f"{name}: an integer >= 1 expected, got {v!r}")
+        if window % pools:
+            raise ValueError(f"a pool count that divides window = {window} expected, got {pools}")
+        if not 0.0 < float(floor) < float("inf"):
+            raise ValueError(f"a finite floor > 0 expected, got {floor}")
+        self.weight, self.lo, self.hi = mel_filterbank(_MEL_BINS, bands, f_min, f_max)
+        self.bands, self.pools, self.window, self.hop, self.floor = bands, pools, window, hop, float(floor)
+        self.dims = bands * pools
+        self._dev = {}   # device -> weight on it
+
+    def windows(self, length: int) -> int:
+        """rows a waveform of `length` samples gives (0: shorter than one window)"""
+        return mel_ops.pool_windows(mel_ops.mel_frames(length), self.window, self.hop)
+
+    def power(self, waves: torch.Tensor) -> torch.Tensor:
+        """(B, L) float32 cuda -> the mel power (B, bands, 1 + L // 256)"""
+        if not isinstance(waves, torch.Tensor) or waves.dim() != 2 or waves.shape[0] < 1:
+            raise ValueError(f"waveforms (B, L) expected, got {tuple(waves.shape) if isinstance(waves, torch.Tensor) else waves!r}")
+        if self.windows(waves.shape[1]) < 1:
+            raise ValueError(f"{waves.shape[1]} samples are fewer than one window of {self.window} frames "
+                             f"({256 * (self.window - 1)} samples)")
+        ops._chk_typed("WaveLogMel", waves)
+        if waves.device not in self._dev:
+            self._dev[waves.device] = self.weight.to(waves.device)
+        return mel_ops.mel_power(waves, self._dev[waves.device], self.lo, self.hi)
+
+    def pool(self, power: torch.Tensor) -> torch.Tensor:
+        """the mel power (B, bands, T) of `power()` -> rows (B * W, bands * pools)"""
+        return mel_ops.logmel_pool(power, self.window, self.hop, self.pools, self.floor)
+
+    def __call__(self, waves: torch.Tensor) -> torch.Tensor:
+        return self.pool(self.power(waves))
 
 
 def _sym_f64(name: str, mean, cov) -> int:
