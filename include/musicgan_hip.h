@@ -932,6 +932,25 @@ int mg_mel_power(const float* wave, int64_t rows, int64_t length, int64_t row_st
 int mg_logmel_pool(const float* power, int64_t rows, int bands, int64_t frames, int win, int hop, int pools, double floor, float* out,
                    mg_stream_t stream);
 
+/* ---- perceptual path length (csrc/ppl.hip): the kernels behind musicgan_amd/ppl_ops.py and metrics.PPL, which the reference does
+ * not have (definition and error bounds: DESIGN.md 4.22).
+ * slerp_pairs: z0, z1 (n, d) float32, t (n) float64, any d >= 1.  za[i] = slerp(z0[i], z1[i], t[i]) and zb[i] = slerp(z0[i], z1[i],
+ *   t[i] + eps), both (n, d) float32, with slerp the definition of project.slerp: each row one flat vector, float64 arithmetic, the
+ *   straight line (1 - t) a + t b below an angle of 1e-6 (equal or nearly parallel rows, a zero row), one rounding to float32;
+ *   t[i] = 0 gives za[i] = z0[i] bit for bit.  flag (n) int32: 1 where the angle is within 1e-6 of pi (no single shortest arc), and
+ *   za[i], zb[i] are then +0.0; else 0.  Every element of za, zb and flag is written.  |z0|^2, |z1|^2 and z0.z1 are float64 sums in
+ *   an order that depends on d alone (lane l of the pair's wave adds the components 4 l .. 4 l + 3, 4 l + 256 .. in ascending order,
+ *   then one butterfly over the 64 lanes), the same whether the rows are 16-byte aligned or not; the same bits in every run and for
+ *   any n.  One launch, one wave per pair, no workspace, no atomics, capturable.
+ * rows_sqdist: a, b (n, d) float32 -> out (n) float64, every element written:
+ *     out[i] = scale * sum_j ((double)a[i,j] - (double)b[i,j])^2
+ *   in the same fixed order (one wave per pair): out[i] is a function of its two rows, d and scale alone -- not of n or of the other
+ *   rows -- and the same bits in every run; exactly 0 for equal finite rows; a NaN or an infinity stays in its pair.  One launch, no
+ *   workspace, no atomics, capturable. */
+int mg_slerp_pairs(const float* z0, const float* z1, const double* t, int64_t n, int64_t d, double eps, float* za, float* zb,
+                   int32_t* flag, mg_stream_t stream);
+int mg_rows_sqdist(const float* a, const float* b, int64_t n, int64_t d, double scale, double* out, mg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,11 +3,12 @@ and the STFT / magnitude-phase codec, hand-written HIP behind a C ABI (include/m
 surface (`networks`, `audio`, `train`, `generate`, `create_dataset`, `view_audio`) on top, plus `evaluate` / `metrics`
 (sliced Wasserstein distance of a checkpoint's samples to the data) and `evaluate_mel` (Frechet distance, Kernel Inception Distance and kNN
 metrics of log-mel spectrograms, of the images, or in `evaluate_mel_waveform` of the sound they decode to) and `evaluate_audio` (the same
-metrics between two sets of audio files), which the reference does not have."""
+metrics between two sets of audio files) and `path_length` (the perceptual path length of a checkpoint's latent space in those rows), which
+the reference does not have."""
 
 
 def __getattr__(name):  # lazy: importing the package must not drag in the data/IO stack
-    if name in ("train", "generate", "create_dataset", "view_audio", "evaluate", "evaluate_mel", "evaluate_audio"):
+    if name in ("train", "generate", "create_dataset", "view_audio", "evaluate", "evaluate_mel", "evaluate_audio", "path_length"):
         import importlib
         fn = getattr(importlib.import_module(f".{name}", __name__), name)
         globals()[name] = fn  # the import system bound the sub-module under this name; re-bind the function like the reference

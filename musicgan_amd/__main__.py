@@ -1,5 +1,5 @@
 """`python -m musicgan_amd <mode> ...`: the reference's four sub-commands with its positional names and flags
-(/root/reference/music_gan/__main__.py:11-124) and `evaluate`, `loudness`, `separate`, `project`, `evaluate_mel` and `evaluate_audio`, which the reference does not have, declared as data and dispatched
+(/root/reference/music_gan/__main__.py:11-124) and `evaluate`, `loudness`, `separate`, `project`, `evaluate_mel`, `evaluate_audio` and `path_length`, which the reference does not have, declared as data and dispatched
 lazily (importing `train` pulls in the GPU library, `view_audio` pulls in matplotlib)."""
 import argparse
 import importlib
@@ -52,6 +52,16 @@ def _probability(text: str):
     if not 0.0 <= p <= 1.0:
         raise argparse.ArgumentTypeError(f"a probability in [0, 1] expected, got {text!r}")
     return p
+
+
+def _step(text: str):
+    try:
+        eps = float(text)
+    except ValueError:
+        eps = 0.0
+    if not 0.0 < eps <= 0.1:
+        raise argparse.ArgumentTypeError(f"a step in (0, 0.1] expected, got {text!r}")
+    return eps
 
 
 # mode -> (module, function, [(flags, kwargs)], lambda args: positional call arguments[, lambda args: keyword call arguments])
@@ -267,9 +277,32 @@ _FEATURE_MODES = {
                        **({"griffin_lim": a.griffin_lim} if a.griffin_lim else {}))),
 }
 
+# sub-commands that measure a checkpoint's latent space, with no dataset involved (same declaration; kept apart as well)
+_PATH_MODES = {
+    "path_length": ("path_length", "path_length", [
+        (("gen_dict_state",), dict(type=str)),
+        (("rand_channels",), dict(type=int)),
+        (("--level",), dict(type=int, default=7, help="growth level of the checkpoint, 4 .. 7 (7: fully grown, 512 x 512)")),
+        (("-n", "--nb-pairs"), dict(dest="nb_pairs", type=int, default=8192, help="pairs of latents (four images each)")),
+        (("--epsilon",), dict(type=_step, default=1e-4, help="the step along the arc between two latents, in (0, 0.1]")),
+        (("--sampling",), dict(choices=("full", "end"), default="full",
+                               help="full: the step starts at a random position of the arc; end: at its first latent")),
+        (("--seed",), dict(type=int, default=0)),
+        (("--waveform",), dict(action="store_true",
+                               help="take every row from the waveform its image decodes to instead of from the magnitude channel, "
+                                    "so that the phase channel counts (level 7 only)")),
+        (("--griffin-lim",), dict(dest="griffin_lim", type=int, default=0, metavar="N",
+                                  help="with --waveform: N rounds of Griffin-Lim phase refinement on every image before it is scored")),
+        (("-o", "--output"), dict(type=str, default=None, help="also write the result as JSON to this file")),
+    ], lambda a: (a.gen_dict_state, a.rand_channels),
+        lambda a: dict(level=a.level, nb_pairs=a.nb_pairs, epsilon=a.epsilon, sampling=a.sampling, seed=a.seed, output=a.output,
+                       **({"waveform": True} if a.waveform else {}),
+                       **({"griffin_lim": a.griffin_lim} if a.griffin_lim else {}))),
+}
+
 
 def _all_modes() -> dict:
-    return {**_MODES, **_FILE_MODES, **_LATENT_MODES, **_FILE_SET_MODES, **_FEATURE_MODES}
+    return {**_MODES, **_FILE_MODES, **_LATENT_MODES, **_FILE_SET_MODES, **_PATH_MODES, **_FEATURE_MODES}
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -288,7 +321,7 @@ def build_parser() -> argparse.ArgumentParser:
 def main(argv=None) -> None:
     parser = build_parser()
     args = parser.parse_args(argv)
-    if args.mode == "evaluate_mel" and args.griffin_lim and not args.waveform:
+    if args.mode in ("evaluate_mel", "path_length") and args.griffin_lim and not args.waveform:
         parser.error("--griffin-lim needs --waveform")
     if args.mode == "generate" and args.loudness is None and (
             args.limiter or args.limiter_attack is not None or args.limiter_release is not None):

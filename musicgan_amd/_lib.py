@@ -259,6 +259,8 @@ SIGNATURES = {
     "mg_standardise_rows": (c_int, [_P, c_int64, c_int64, _P, _P, _P, _P]),
     "mg_polyk_ws_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
     "mg_polyk_rowsums": (c_int, [_P, c_int64, _P, c_int64, _P, _P, c_int64, c_int64, c_int64, c_int64, c_int, _P, _P, c_size_t, _P]),
+    "mg_slerp_pairs": (c_int, [_P, _P, _P, c_int64, c_int64, ctypes.c_double, _P, _P, _P, _P]),
+    "mg_rows_sqdist": (c_int, [_P, _P, c_int64, c_int64, ctypes.c_double, _P, _P]),
 }
 
 _lib = None

@@ -76,7 +76,16 @@ kernels: csrc/kid.hip through musicgan_amd/kid_ops.py -- no kernel matrix is sto
 (8) The same rows taken from waveforms, where the phase counts: WaveLogMel.  Definition and error bound: DESIGN.md 4.21; kernels:
 csrc/melspec.hip through mel_ops.mel_power and mel_ops.logmel_pool.
 
-    rows = WaveLogMel(pools=8)(waves)             # (B, L) float32 cuda -> (B * W, 64 * 8): a row per window of 512 frames"""
+    rows = WaveLogMel(pools=8)(waves)             # (B, L) float32 cuda -> (B * W, 64 * 8): a row per window of 512 frames
+
+(9) The perceptual path length (Karras et al., "A Style-Based Generator Architecture for GANs", CVPR 2019) with the squared distance
+of those rows in the place of LPIPS: how fast the output moves when the latent moves a small step along an interpolation arc.
+It needs a generator only, no data.  Definition and error bounds: DESIGN.md 4.22; kernels: csrc/ppl.hip through musicgan_amd/ppl_ops.py.
+
+    ppl = PPL(rows_of, rand_channels=32)          # rows_of: latents (B, 32, 2, 2) float32 cuda -> rows (B, D) float32 cuda
+    ppl.feed(8192)                                # pairs; any split
+    ppl.result()                                  # {"ppl": .., "ppl_mean": .., "ppl_chord": .., "ppl_ratio": .., "ppl_pairs": ..}
+    ppl.per_pair()                                # (pairs,) float64 cuda"""
 from __future__ import annotations
 
 import math
@@ -85,7 +94,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
-from . import kid_ops, km_ops, mel_ops, nn_ops, ops, ssim_ops
+from . import kid_ops, km_ops, mel_ops, nn_ops, ops, ppl_ops, ssim_ops
 
 
 def pyramid_sides(side_h: int, side_w: int, min_side: int = 16) -> List[Tuple[int, int]]:
@@ -1090,3 +1099,131 @@ class KID:
             return {"kid": full, "kid_std": 0.0, "kid_full": full}    # the one subset there is: the whole sets
         kid, std = kid_subsets(real, fake, self.subsets, self.subset_size, self.seed)
         return {"kid": kid, "kid_std": std, "kid_full": full}
+
+
+# ------------------------------------------------------------------ perceptual path length (PPL)
+def ppl_trim(values: Sequence[float]) -> Tuple[float, float]:
+    """(lo, hi) of the StyleGAN protocol for the finite-count list `values`: the elements of rank floor(0.01 (n - 1)) and
+    ceil(0.99 (n - 1)) of the sorted list -- numpy.percentile(values, 1, 'lower') and numpy.percentile(values, 99, 'higher'), in
+    integer arithmetic"""
+    ordered, last = sorted(values), len(values) - 1
+    return ordered[last // 100], ordered[-((-99 * last) // 100)]
+
+
+class PPL:
+    """The perceptual path length of a generator (Karras et al. 2019) in whatever space `rows_of` maps latents to (the log-mel rows
+    of the generated images in path_length).  For pair i: z0_i, z1_i ~ N(0, I) of shape (rand_channels, 2, 2) and
+    t_i ~ U[0, 1) (`sampling` "full") or t_i = 0 ("end"), za_i = slerp(z0_i, z1_i, t_i), zb_i = slerp(z0_i, z1_i, t_i + epsilon)
+    (ppl_ops.slerp_pairs: project.slerp's definition), and with D the row length
+        d_i = |rows_of(za_i) - rows_of(zb_i)|^2 / (D epsilon^2)                     (ppl_ops.rows_sqdist, float64).
+    `rows_of(latents (B, rand_channels, 2, 2) float32 cuda) -> (B, D) float32 cuda` is any callable.  It is always called with 16
+    latents (the last call: the rest), za_i and zb_i next to each other: a generator's kernels are chosen by the batch size, and
+    the two images of a pair must come from the same launches.
+
+    `feed(n_pairs)` only counts: z0, z1 and t are one draw each, of all pairs fed, from one device generator seeded with `seed`, so
+    the draws need the total and every launch waits for per_pair() / result().  Any split of the feeds gives the same bits.
+
+    result(): `ppl` = the mean of the d_i with lo <= d_i <= hi (ppl_trim), `ppl_mean` = the mean of all d_i, and with "full"
+    sampling `ppl_chord` = the mean of |rows_of(z0_i) - rows_of(z1_i)|^2 / D and `ppl_ratio` = ppl_mean / ppl_chord, which is >= 1
+    in expectation and 1 for straight paths of constant speed in row space (NaN when ppl_chord is 0); `ppl_pairs` = the pairs
+    used: a pair whose ends are antipodal (an angle within 1e-6 of pi) has no single shortest arc and is left out of every mean.
+    All values reach the host in one copy; the means are math.fsum(kept) / count there: exactly rounded, whatever the order."""
+
+    PAIRS_PER_CALL = 8   # 16 images per call of rows_of
+
+    def __init__(self, rows_of, epsilon: float = 1e-4, sampling: str = "full", seed: int = 0, *, rand_channels: int) -> None:
+        if not callable(rows_of):
+            raise ValueError(f"rows_of: a callable (B, C, 2, 2) -> (B, D) expected, got {rows_of!r}")
+        if not _is_int(rand_channels) or rand_channels < 1:
+            raise ValueError(f"rand_channels >= 1 expected, got {rand_channels!r}")
+        if isinstance(epsilon, bool) or not isinstance(epsilon, (int, float)) or not 0.0 < epsilon <= 0.1:
+            raise ValueError(f"epsilon in (0, 0.1] expected, got {epsilon!r}")
+        if sampling not in ("full", "end"):
+            raise ValueError(f"sampling: \"full\" or \"end\" expected, got {sampling!r}")
+        if not _is_int(seed):
+            raise ValueError(f"an integer seed expected, got {seed!r}")
+        self.rows_of, self.rand_channels, self.epsilon, self.sampling, self.seed = rows_of, rand_channels, float(epsilon), sampling, seed
+        self.pairs, self.dims, self._values = 0, None, None
+
+    def feed(self, n_pairs: int) -> None:
+        if not _is_int(n_pairs) or n_pairs < 1:
+            raise ValueError(f"feed: a number of pairs >= 1 expected, got {n_pairs!r}")
+        self.pairs += n_pairs
+        self._values = None
+
+    def _distances(self, first: torch.Tensor, second: torch.Tensor, scale_of) -> torch.Tensor:
+        """(n,) float64: scale_of(D) |rows_of(first_i) - rows_of(second_i)|^2, the two latents of a pair adjacent in their call"""
+        n, per = first.shape[0], self.PAIRS_PER_CALL
+        a = b = None
+        for lo in range(0, n, per):
+            hi = min(lo + per, n)
+            latents = torch.stack([first[lo:hi], second[lo:hi]], 1).reshape(2 * (hi - lo), self.rand_channels, 2, 2)
+            rows = self.rows_of(latents.contiguous())
+            if not isinstance(rows, torch.Tensor) or rows.dim() != 2 or rows.shape[0] != 2 * (hi - lo) or rows.shape[1] < 1:
+                raise ValueError(f"PPL: rows_of: rows ({2 * (hi - lo)}, D) expected, got "
+                                 f"{tuple(rows.shape) if isinstance(rows, torch.Tensor) else rows!r}")
+            if a is None:
+                self.dims = int(rows.shape[1])
+                a = torch.empty((n, self.dims), dtype=torch.float32, device=rows.device)
+                b = torch.empty((n, self.dims), dtype=torch.float32, device=rows.device)
+            elif rows.shape[1] != self.dims:
+                raise ValueError(f"PPL: rows_of: rows of {self.dims} numbers expected, got {rows.shape[1]}")
+            pairs = rows.view(hi - lo, 2, self.dims)
+            a[lo:hi].copy_(pairs[:, 0])
+            b[lo:hi].copy_(pairs[:, 1])
+        return ppl_ops.rows_sqdist(a, b, scale_of(self.dims))
+
+    def _run(self):
+        if self._values is None:
+            if self.pairs < 1:
+                raise ValueError("PPL: no pairs fed")
+            n, d = self.pairs, self.rand_channels * 4
+            device = torch.device("cuda", torch.cuda.current_device())
+            rng = torch.Generator(device=device).manual_seed(self.seed)
+            z0 = torch.randn(n, d, device=device, generator=rng)
+            z1 = torch.randn(n, d, device=device, generator=rng)
+            if self.sampling == "full":
+                t = torch.rand(n, dtype=torch.float64, device=device, generator=rng)
+            else:
+                t = torch.zeros(n, dtype=torch.float64, device=device)
+            za, zb, flag = ppl_ops.slerp_pairs(z0, z1, t, self.epsilon)
+            step = self._distances(za, zb, lambda dims: 1.0 / (dims * self.epsilon * self.epsilon))
+            chord = self._distances(z0, z1, lambda dims: 1.0 / dims) if self.sampling == "full" else None
+            self._values = step, chord, flag
+        return self._values
+
+    def per_pair(self) -> torch.Tensor:
+        """(pairs,) float64 on the device: d_i, NaN for a pair that is left out"""
+        step, _, flag = self._run()
+        return torch.where(flag != 0, torch.full_like(step, float("nan")), step)
+
+    def per_pair_chord(self) -> Optional[torch.Tensor]:
+        """(pairs,) float64 on the device: |rows_of(z0_i) - rows_of(z1_i)|^2 / D, NaN for a pair that is left out; None with "end"
+        sampling"""
+        _, chord, flag = self._run()
+        return None if chord is None else torch.where(flag != 0, torch.full_like(chord, float("nan")), chord)
+
+    def flags(self) -> torch.Tensor:
+        """(pairs,) int32 on the device: 1 for a pair that is left out (antipodal ends)"""
+        return self._run()[2]
+
+    def result(self) -> Dict[str, float]:
+        step, chord, flag = self._run()
+        columns = [step, flag.to(torch.float64)] + ([chord] if chord is not None else [])
+        host = torch.stack(columns).cpu().tolist()   # the one copy
+        return ppl_aggregate(host[0], host[1], host[2] if chord is not None else None)
+
+
+def ppl_aggregate(step: Sequence[float], flag: Sequence[float], chord: Optional[Sequence[float]] = None) -> Dict[str, float]:
+    """PPL.result()'s keys from the per-pair values on the host (float64 lists; flag != 0: the pair is left out)"""
+    kept = [v for v, f in zip(step, flag) if not f]
+    if not kept:
+        raise ValueError("PPL: every pair was left out (antipodal ends)")
+    lo, hi = ppl_trim(kept)
+    inner = [v for v in kept if lo <= v <= hi]
+    result = {"ppl": math.fsum(inner) / len(inner) if inner else float("nan"), "ppl_mean": math.fsum(kept) / len(kept)}
+    if chord is not None:
+        result["ppl_chord"] = math.fsum(v for v, f in zip(chord, flag) if not f) / len(kept)
+        result["ppl_ratio"] = result["ppl_mean"] / result["ppl_chord"] if result["ppl_chord"] > 0.0 else float("nan")
+    result["ppl_pairs"] = len(kept)
+    return result
